@@ -8,15 +8,18 @@ BASELINE config 2 (a 2^26-float bucket) is timed under extras.othe
 With --gpus N > 1 every rank encodes its own 2^28-float gradient (weak scaling) and the step adds
 the RCCL all-gather of the compressed payloads over xGMI.  `value` = fp32-input GB/s of the whole job.
 
-Extra fields: decode GB/s and decode L2 error (the metric's "+ decode L2 err"), per-kernel
-device times, the roofline of the dominant kernel, the CPU baseline (the C restatement of the
-reference Java algorithm, oracle/, timed on this host on a bounded sample) and the
-H2D/D2H-inclusive rate.
+A plain run sets up, warms up, times --steps encodes, writes --dump-outputs if asked and prints
+the result line (value, ms_per_step).  Everything else is measured only with --full, after the
+headline and outside its timed region: decode GB/s and decode L2 error (the metric's "+ decode L2
+err"), per-kernel device times, the roofline of the dominant kernel, the other configurations, the
+CPU baseline (the C restatement of the reference Java algorithm, oracle/, timed on this host on a
+bounded sample) and the H2D/D2H-inclusive rate.
 """
 import argparse
 import ctypes as C
 import glob
 import json
+import math
 import os
 import statistics
 import sys
@@ -50,11 +53,18 @@ def parse():
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32",
                     help="input dtype (f64 = the reference's double[] path)")
     ap.add_argument("--quant", choices=["quantile", "uniform"], default="quantile")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline budget (both legs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip decode / H2D measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what the line reports under roofline, extras and "
+                         "cpu_baseline: per-kernel times, decode, the host path, the other configurations, the "
+                         "N > 1 exchange checks and the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step produced (the payload's header, splits and packed "
+                         "codes) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline budget (both legs; with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip decode / H2D measurements")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the fp64 and C3 sparse measurements reported under extras.other_configs")
+                    help="with --full: skip the fp64 and C3 sparse measurements reported under extras.other_configs")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: every rank joins a gloo group and reports itself")
     return ap.parse_args()
@@ -568,6 +578,47 @@ def host_path_rates(lib, ctx, x, n, params, reps=5):
     return res
 
 
+DUMP_SAMPLE = 2**22  # code bytes kept per payload by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(outdir, lib, ctx, payload, gathered, world, slot_bytes):
+    """--dump-outputs: what the caller of the timed step holds after its last step, as .npy files.
+    header.npy (float64: n, bin_num, zero_idx, code_bits, req_bins, min, max), splits.npy (float64,
+    bin_num - 1 split points) and codes.npy (float32: the packed code bytes, all of them up to
+    DUMP_SAMPLE bytes, else the bytes at DUMP_SAMPLE fixed positions drawn with a seeded generator)
+    of the payload the last step wrote.  With the N > 1 exchange also gathered_codes.npy: the same
+    bytes of every rank's slot of the all-gathered buffer, one row per rank."""
+    from sketchml_amd import _lib
+    os.makedirs(outdir, exist_ok=True)
+
+    def parts(ptr, count):
+        hdr = _lib.DenseHeader()
+        splits = np.zeros(_lib.SKML_MAX_BINS, dtype=np.float64)
+        st = lib.skml_dense_info(ctx, C.c_void_p(ptr), C.byref(hdr), splits.ctypes.data_as(_lib.dblp), len(splits))
+        if st:
+            raise RuntimeError(_lib.last_error())
+        ncode = (hdr.n * hdr.code_bits + 7) // 8
+        if ncode <= count:
+            pos = np.arange(ncode, dtype=np.int64)
+        else:
+            pos = np.sort(np.random.default_rng(20240607).integers(0, ncode, size=count, dtype=np.int64))
+        return hdr, splits[:max(0, hdr.bin_num - 1)], pos + hdr.codes_offset
+
+    hdr, splits, pos = parts(payload.data_ptr(), DUMP_SAMPLE)
+    codes = payload[torch.from_numpy(pos).to(payload.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(outdir, "header.npy"),
+            np.array([hdr.n, hdr.bin_num, hdr.zero_idx, hdr.code_bits, hdr.req_bins, hdr.min, hdr.max], dtype=np.float64))
+    np.save(os.path.join(outdir, "splits.npy"), splits)
+    np.save(os.path.join(outdir, "codes.npy"), codes)
+    if gathered is not None:
+        rows = []
+        for r in range(world):
+            _, _, pos = parts(gathered.data_ptr() + r * slot_bytes, DUMP_SAMPLE // world)
+            rows.append(gathered[torch.from_numpy(pos + r * slot_bytes).to(gathered.device)].cpu().numpy())
+        width = min(len(row) for row in rows)
+        np.save(os.path.join(outdir, "gathered_codes.npy"), np.stack([row[:width] for row in rows]).astype(np.float32))
+
+
 def _workload_label(args, world):
     """config.workload from the run's own arguments (BASELINE configs named where they match)."""
     n, bins = args.n, args.bins
@@ -726,6 +777,9 @@ def main():
         t = torch.tensor([extra], device=dev, dtype=torch.int64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         extra = int(t.item())
+    # the timed region starts on bucket 0 and payload buffer 0 whatever the warm-up's length was,
+    # so its last step encodes the same bucket in every run (--dump-outputs compares run with run)
+    extra += -(nwarm + extra) % math.lcm(nbuf, len(payloads))
     for i in range(extra):
         step(nwarm + i)
     nwarm += extra
@@ -748,6 +802,39 @@ def main():
 
     # the headline: K encodes, nothing else on the stream
     elapsed = timed_region(nwarm)
+    ms_per_step = 1000.0 * elapsed / args.steps
+    value = world * esize * n * args.steps / elapsed / 1e9
+    last = payloads[(nwarm + args.steps - 1) % len(payloads)]  # what the last timed step wrote
+    hdr = _lib_header(lib, ctx, last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lib, ctx, last, allp if exch is not None else None, world, nb)
+
+    def report(roofline, cpu, extras):
+        barrier()
+        if exch is not None:
+            exch.close()
+        if rank == 0:
+            line = {
+                "metric": "device-resident grad encode GB/s (fp32 in) + decode L2 err, 1/2/4/8 GPU",
+                "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "warmup_steps_run": nwarm, "ms_per_step": round(ms_per_step, 4),
+                "higher_is_better": True,
+                "warmup_note": f"{nwarm} untimed encodes: --warmup {args.warmup}, extended to {args.warmup_ms:g} ms of "
+                               "sustained load so the engine clock has settled (profiles/r05b_warmup_ramp.txt)",
+                "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic N(0,1), torch generator",
+                "config": {"workload": _workload_label(args, world),
+                           "n_per_gpu": n, "bins": bins, "rotating_buffers": nbuf, "parallelism": f"dp{world}"},
+                "full": args.full, "roofline": roofline, "cpu_baseline": cpu, "extras": extras,
+            }
+            print(json.dumps(line))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: the roofline, the per-kernel times, decode, the other configurations
+        # and the CPU baseline take runs of their own (--full)
+        return report(None, None, {"warmup_steps_run": nwarm, "bin_num_effective": hdr.bin_num,
+                                   "code_bits": hdr.code_bits})
     # the same K encodes again with HIP events around the leaf launches only (on the codec
     # stream): the live kernel time of the roofline, measured outside the headline's region
     lib.skml_ctx_set_timing(ctx, 1 << 0)
@@ -764,9 +851,6 @@ def main():
     lib.skml_ctx_set_timing(ctx, 0)
     allstats = kernel_stats(lib, ctx)
     steps_b = min(args.steps, 10)
-
-    ms_per_step = 1000.0 * elapsed / args.steps
-    value = world * esize * n * args.steps / elapsed / 1e9
 
     # ---- roofline of the dominant kernel (algorithmic bytes per launch / avg duration) ----
     hdr = _lib.DenseHeader()
@@ -885,27 +969,7 @@ def main():
         # after every timed GPU region (the other ranks wait at the barrier below)
         cpu = cpu_baseline(xs[0][: 2**24].cpu().numpy(), bins, args.cpu_seconds)
 
-    barrier()
-    if exch is not None:
-        exch.close()
-    if rank == 0:
-        line = {
-            "metric": "device-resident grad encode GB/s (fp32 in) + decode L2 err, 1/2/4/8 GPU",
-            "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "warmup_steps_run": nwarm, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "warmup_note": f"{nwarm} untimed encodes: --warmup {args.warmup}, extended to {args.warmup_ms:g} ms of "
-                           "sustained load so the engine clock has settled (profiles/r05b_warmup_ramp.txt)",
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic N(0,1), torch generator",
-            "config": {"workload": _workload_label(args, world),
-                       "n_per_gpu": n, "bins": bins, "rotating_buffers": nbuf, "parallelism": f"dp{world}"},
-            "roofline": roofline, "cpu_baseline": cpu, "extras": extras,
-        }
-        print(json.dumps(line))
-    if exch is not None:
-        exch.close()
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    report(roofline, cpu, extras)
 
 
 if __name__ == "__main__":

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_exchange_step_world1():
     env = dict(os.environ, SKML_BENCH_EXCHANGE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(1 << 22), "--steps", "4",
-                          "--warmup", "2", "--no-cpu-baseline", "--no-configs"],
+                          "--warmup", "2", "--full", "--no-cpu-baseline", "--no-configs"],
                          capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

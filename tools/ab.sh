@@ -1,7 +1,7 @@
 #!/bin/bash
 # Alternating A/B runs on the GPU box (through gpurun): the one parameterised driver for every A/B.
 #   bash tools/ab.sh TAG REPS KIND VARIANT...
-# KIND: dense  -> bench.py encode only (--steps 100, no extras)
+# KIND: dense  -> bench.py --full, encode and its per-kernel times only (--steps 100, no extras)
 #       sparse -> tools/bench_sparse.py --reps 10 --aggregate 8 (8 distinct C3 payloads)
 #       dsum   -> tools/bench_decode_sum.py
 #       gap    -> tools/leaf_gap.py --steps 20 --reps 2 (gap26 / gap24: at 2^26 / 2^24 floats)
@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/ab_$TAG
 mkdir -p "$OUT"
 case $KIND in
-  dense)  CMD="python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extras --no-configs" ;;
+  dense)  CMD="python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-extras --no-configs" ;;
   sparse) CMD="python tools/bench_sparse.py --reps 10 --aggregate 8" ;;
   dsum)   CMD="python tools/bench_decode_sum.py" ;;
   gap)    CMD="python tools/leaf_gap.py --steps 20 --reps 2" ;;

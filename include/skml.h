@@ -161,6 +161,16 @@ int skml_dense_encode_f32(skml_ctx* ctx, const float* x_dev, int64_t n, const sk
 int skml_dense_encode_f64(skml_ctx* ctx, const double* x_dev, int64_t n, const skml_params* params,
                           void* payload_dev, size_t payload_cap);
 
+/* The same on bf16 / fp16 input (torch.bfloat16 / torch.float16 gradients; 16-bit values travel
+ * as uint16_t).  Widening a 16-bit float to fp32 is exact for every bit pattern, so the result is
+ * defined as skml_dense_encode_f32 of the widened buffer and the payload is byte for byte the
+ * same; the kernels widen in registers and no fp32 copy is made.  Arguments, params->dedup /
+ * seed and status codes as skml_dense_encode_f32 (x_dev 16-byte aligned).  Asynchronous. */
+int skml_dense_encode_bf16(skml_ctx* ctx, const uint16_t* x_dev, int64_t n, const skml_params* params,
+                           void* payload_dev, size_t payload_cap);
+int skml_dense_encode_f16(skml_ctx* ctx, const uint16_t* x_dev, int64_t n, const skml_params* params,
+                          void* payload_dev, size_t payload_cap);
+
 /* UniformQuantizer.quantize(double[]) (quantization/UniformQuantizer.java:21-45): min / max
  * (Double.MAX_VALUE / Double.MIN_VALUE initialised, NaN values skipped), bin_num-1 splits by
  * repeated `+= (max-min)/bin_num`, findZeroIdx, bins[i] = indexOf(x[i]).  No Maths.unique; NaN
@@ -222,6 +232,12 @@ int skml_dense_encode_with_splits_f32(skml_ctx* ctx, const float* x_dev, int64_t
  * out[i] = (float) Quantizer.getValues()[bin[i]].  Asynchronous. */
 int skml_dense_decode_f32(skml_ctx* ctx, const void* payload_dev, float* out_dev, int64_t n);
 
+/* decompressDense into bf16 / fp16: skml_dense_decode_f32's float rounded to nearest even.  Any
+ * payload decodes to any output type.  out_dev needs 2-byte alignment only (16-byte stores when it
+ * is 16-byte aligned, element stores otherwise).  Asynchronous. */
+int skml_dense_decode_bf16(skml_ctx* ctx, const void* payload_dev, uint16_t* out_dev, int64_t n);
+int skml_dense_decode_f16(skml_ctx* ctx, const void* payload_dev, uint16_t* out_dev, int64_t n);
+
 /* decompressDense into double[] (the reference's return type): out[i] = getValues()[bin[i]]
  * without the float rounding.  Asynchronous. */
 int skml_dense_decode_f64(skml_ctx* ctx, const void* payload_dev, double* out_dev, int64_t n);
@@ -232,6 +248,13 @@ int skml_dense_decode_f64(skml_ctx* ctx, const void* payload_dev, double* out_de
  * out `stride` bytes apart.  Asynchronous. */
 int skml_dense_decode_sum_f32(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride,
                               float* out_dev, int64_t n, double scale);
+
+/* The same sum (in double, payload order, times scale, cast to float) rounded to nearest even
+ * into a bf16 / fp16 output; out_dev as in skml_dense_decode_bf16.  Asynchronous. */
+int skml_dense_decode_sum_bf16(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride,
+                               uint16_t* out_dev, int64_t n, double scale);
+int skml_dense_decode_sum_f16(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride,
+                              uint16_t* out_dev, int64_t n, double scale);
 
 /* Quantizer.getBins() (Quantizer.java:168-170): materialise int32 bins on the device. */
 int skml_dense_bins_i32(skml_ctx* ctx, const void* payload_dev, int32_t* bins_dev, int64_t n);

@@ -64,15 +64,31 @@ def alloc_aligned(nbytes: int, device, align: int = 256) -> torch.Tensor:
     return buf[off: off + nbytes]
 
 
+LOWP_DTYPES = (torch.bfloat16, torch.float16)
+
+
 def as_device_values(values, device=None) -> torch.Tensor:
     """Device-resident contiguous, 16-byte aligned view of a gradient: float64 input (a torch
-    float64 tensor or a numpy float64 array, the reference's double[]) stays fp64; everything
-    else becomes fp32."""
+    float64 tensor or a numpy float64 array, the reference's double[]) stays fp64, a torch
+    bfloat16 / float16 tensor or a numpy float16 array stays in its 16-bit dtype (the encode widens
+    it in registers; callers without a 16-bit entry upcast with as_device_f32); everything else
+    becomes fp32."""
     if isinstance(values, torch.Tensor):
         wide = values.dtype == torch.float64
+        lowp = values.dtype in LOWP_DTYPES
     else:
         import numpy as np
         wide = np.asarray(values).dtype == np.float64
+        lowp = np.asarray(values).dtype == np.float16
+    if lowp:
+        if isinstance(values, torch.Tensor):
+            t = values if values.is_cuda else values.to(device or torch.cuda.current_device())
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(values)).to(device or torch.cuda.current_device())
+        t = t.contiguous().view(-1)
+        if t.data_ptr() % 16:
+            t = t.clone()
+        return t
     if not wide:
         return as_device_f32(values, device)
     if isinstance(values, torch.Tensor):

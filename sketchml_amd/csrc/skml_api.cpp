@@ -582,15 +582,15 @@ namespace {
 // The sketch of x[0, n): leaf + upper merge passes.  summary: the last pass's last workgroup
 // also runs the summary into `payload` (returns *fused = true); otherwise the levels stay in
 // w.roots and the partials in w.part for a caller-side summary or a SketchRecord.
-int run_sketch_f32(skml_ctx* c, const float* x, int64_t n, uint64_t s0, const Workspace& w, const skml_params* p,
-                   void* payload, bool summary, bool* fused_out) {
+int run_sketch_f32(skml_ctx* c, const void* x, int64_t n, uint64_t s0, const Workspace& w, const skml_params* p,
+                   void* payload, bool summary, bool* fused_out, int xtype = kXF32) {
     const int64_t chunks = n / kChunk;
     const int64_t nwg = (chunks + kLeafChunks - 1) / kLeafChunks;  // leaf partials (one per wave tile)
     bool fused = false;
     if (chunks > 0) {
         {
             KernelTimer kt(c, SKML_K_LEAF);
-            HIP_TRY(launch_leaf(c->stream, x, chunks, s0, c->jump_tab, w.part, w.nodes6, w.roots, w.ubits));
+            HIP_TRY(launch_leaf(c->stream, x, chunks, s0, c->jump_tab, w.part, w.nodes6, w.roots, w.ubits, xtype));
         }
         if (c->after_leaf) {
             HIP_TRY(hipEventRecord(c->after_leaf, c->stream));
@@ -611,7 +611,8 @@ int run_sketch_f32(skml_ctx* c, const float* x, int64_t n, uint64_t s0, const Wo
             HIP_TRY(launch_merge_pass(c->stream, passes[i], fuse_next ? &passes[i + 1] : nullptr, src, dst, next_dst,
                                       w.roots, s0, c->jump_tab, w.done, x, n, w.part, nwg, c->ranks, p->bin_num,
                                       p->dedup ? 1 : 0, payload, w.raw, w.lut, w.ubits,
-                                      summary ? w.part_red : nullptr, summary ? nred : 0, summary ? part_from : 0));
+                                      summary ? w.part_red : nullptr, summary ? nred : 0, summary ? part_from : 0,
+                                      xtype));
             src = dst;
             dst = next_dst;
             if (fuse_next) break;
@@ -641,10 +642,10 @@ uint64_t sketch_draws(int64_t n) {
 }
 }  // namespace
 
-extern "C" {
-
-int skml_dense_encode_f32(skml_ctx* c, const float* x, int64_t n, const skml_params* p,
-                          void* payload, size_t cap) {
+// QuantileQuantizer.quantize of x in storage type xtype: the sketch and the quantize pass widen a
+// 16-bit input in registers, everything else is the fp32 encode.
+static int dense_encode_x(skml_ctx* c, const void* x, int xtype, int64_t n, const skml_params* p, void* payload,
+                          size_t cap) {
     skml_params def;
     if (!p) {
         skml_params_default(&def);
@@ -660,17 +661,34 @@ int skml_dense_encode_f32(skml_ctx* c, const float* x, int64_t n, const skml_par
     const uint64_t s0 = ((uint64_t)p->seed ^ kLcgMult) & kLcgMask;
     const int64_t nwg = (chunks + kLeafChunks - 1) / kLeafChunks;
     bool fused = false;
-    if ((st = run_sketch_f32(c, x, n, s0, w, p, payload, true, &fused))) return st;
+    if ((st = run_sketch_f32(c, x, n, s0, w, p, payload, true, &fused, xtype))) return st;
     if (!fused) {
         KernelTimer kt(c, SKML_K_SUMMARY);
         HIP_TRY(launch_summary(c->stream, x, n, w.part, nwg, w.roots, c->ranks, p->bin_num,
-                               p->dedup ? 1 : 0, payload, w.raw, w.lut));
+                               p->dedup ? 1 : 0, payload, w.raw, w.lut, xtype));
     }
     {
         KernelTimer kt(c, SKML_K_QUANTIZE);
-        HIP_TRY(launch_quantize(c->stream, x, n, payload, w.lut, p->bin_num));
+        HIP_TRY(launch_quantize(c->stream, x, n, payload, w.lut, p->bin_num, xtype));
     }
     return SKML_OK;
+}
+
+extern "C" {
+
+int skml_dense_encode_f32(skml_ctx* c, const float* x, int64_t n, const skml_params* p,
+                          void* payload, size_t cap) {
+    return dense_encode_x(c, x, kXF32, n, p, payload, cap);
+}
+
+int skml_dense_encode_bf16(skml_ctx* c, const uint16_t* x, int64_t n, const skml_params* p,
+                           void* payload, size_t cap) {
+    return dense_encode_x(c, x, kXBF16, n, p, payload, cap);
+}
+
+int skml_dense_encode_f16(skml_ctx* c, const uint16_t* x, int64_t n, const skml_params* p,
+                          void* payload, size_t cap) {
+    return dense_encode_x(c, x, kXF16, n, p, payload, cap);
 }
 
 }  // extern "C"
@@ -1180,10 +1198,28 @@ int skml_dense_decode_f32(skml_ctx* c, const void* payload, float* out, int64_t 
     return SKML_OK;
 }
 
-int skml_dense_decode_sum_f32(skml_ctx* c, const void* payloads, int32_t P, size_t stride, float* out,
+// A 16-bit output needs its element's alignment only (the kernels pick 16-byte or element stores).
+static int dense_decode_lowp(skml_ctx* c, const void* payload, uint16_t* out, int64_t n, int otype) {
+    if (!c || !valid_payload_ptr(payload) || (n > 0 && (!out || ((uintptr_t)out) % 2)))
+        return fail(SKML_E_ARG, "bad decode arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    KernelTimer kt(c, SKML_K_DECODE);
+    HIP_TRY(launch_decode(c->stream, payload, out, n, otype));
+    return SKML_OK;
+}
+
+int skml_dense_decode_bf16(skml_ctx* c, const void* payload, uint16_t* out, int64_t n) {
+    return dense_decode_lowp(c, payload, out, n, kXBF16);
+}
+
+int skml_dense_decode_f16(skml_ctx* c, const void* payload, uint16_t* out, int64_t n) {
+    return dense_decode_lowp(c, payload, out, n, kXF16);
+}
+
+static int dense_decode_sum_x(skml_ctx* c, const void* payloads, int32_t P, size_t stride, void* out, int otype,
                               int64_t n, double scale) {
     if (!c || !valid_payload_ptr(payloads) || stride % 256 || P < 1 || P > 16 ||
-        (n > 0 && (!out || ((uintptr_t)out) % 16)))
+        (n > 0 && (!out || ((uintptr_t)out) % (otype == kXF32 ? 16 : 2))))
         return fail(SKML_E_ARG, "bad decode_sum arguments (P in [1,16], 256-B aligned payloads)");
     HIP_TRY(hipSetDevice(c->device));
     // Gradient.sum adds gradients of one dimension (ml/gradient/Gradient.scala:44-49): every
@@ -1209,8 +1245,23 @@ int skml_dense_decode_sum_f32(skml_ctx* c, const void* payloads, int32_t P, size
         max_bins = std::max(max_bins, (int)h[p].bin_num);
     }
     KernelTimer kt(c, SKML_K_DECODE_SUM);
-    HIP_TRY(launch_decode_sum(c->stream, payloads, P, stride, out, n, scale, common_bits, max_bins));
+    HIP_TRY(launch_decode_sum(c->stream, payloads, P, stride, out, n, scale, common_bits, max_bins, otype));
     return SKML_OK;
+}
+
+int skml_dense_decode_sum_f32(skml_ctx* c, const void* payloads, int32_t P, size_t stride, float* out,
+                              int64_t n, double scale) {
+    return dense_decode_sum_x(c, payloads, P, stride, out, kXF32, n, scale);
+}
+
+int skml_dense_decode_sum_bf16(skml_ctx* c, const void* payloads, int32_t P, size_t stride, uint16_t* out,
+                               int64_t n, double scale) {
+    return dense_decode_sum_x(c, payloads, P, stride, out, kXBF16, n, scale);
+}
+
+int skml_dense_decode_sum_f16(skml_ctx* c, const void* payloads, int32_t P, size_t stride, uint16_t* out,
+                              int64_t n, double scale) {
+    return dense_decode_sum_x(c, payloads, P, stride, out, kXF16, n, scale);
 }
 
 int skml_dense_bins_i32(skml_ctx* c, const void* payload, int32_t* bins, int64_t n) {

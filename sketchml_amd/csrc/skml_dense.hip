@@ -48,6 +48,36 @@ __device__ __forceinline__ void store_codes4(uint8_t* codes, int64_t e0, uint32_
     }
 }
 
+// Eight consecutive codes of one lane starting at e0 (a multiple of 8): the 16-bit input forms,
+// whose lanes hold 8 values per 16-byte load.
+__device__ __forceinline__ void store_codes8(uint8_t* codes, int64_t e0, const uint32_t (&c)[8], int bits) {
+    switch (bits) {
+        case 8: {
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 w = {c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24)};
+            __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(codes + e0));
+            break;
+        }
+        case 16:
+            *reinterpret_cast<uint4*>(codes + e0 * 2) =
+                make_uint4(c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16));
+            break;
+        case 4:
+            *reinterpret_cast<uint32_t*>(codes + e0 / 2) = c[0] | (c[1] << 4) | (c[2] << 8) | (c[3] << 12) | (c[4] << 16) |
+                                                           (c[5] << 20) | (c[6] << 24) | (c[7] << 28);
+            break;
+        case 2:
+            __builtin_nontemporal_store((uint16_t)(c[0] | (c[1] << 2) | (c[2] << 4) | (c[3] << 6) | (c[4] << 8) |
+                                                   (c[5] << 10) | (c[6] << 12) | (c[7] << 14)),
+                                        reinterpret_cast<uint16_t*>(codes + e0 / 4));
+            break;
+        default:
+            codes[e0 / 8] = (uint8_t)(c[0] | (c[1] << 1) | (c[2] << 2) | (c[3] << 3) | (c[4] << 4) | (c[5] << 5) |
+                                      (c[6] << 6) | (c[7] << 7));
+            break;
+    }
+}
+
 // Search modes of the quantize pass, chosen per launch from the header and the bucket LUT:
 //   kModeLut<S>  bin = base[key >> 18] then S bisection steps over the LDS split table
 //   kModeEytz    branchless Eytzinger descent over the LDS split table (cmax too large)
@@ -101,14 +131,60 @@ __device__ __forceinline__ uint32_t quant_bin(const QuantTables& q, float xv) {
 #endif
 constexpr int kQStageWords = 256;  // per wave: 1,024 one-byte codes
 
-template <int MODE>
-__device__ __forceinline__ void quant_tiles(const QuantTables& q, const float* __restrict__ x, int64_t n,
+// X: the storage type of x.  A 16-bit tile of 1,024 values is 2 KiB: two 16-byte loads (8 values
+// each) per lane, widened in registers; quant_bin sees the same floats as the fp32 form.
+template <int MODE, typename X = float>
+__device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __restrict__ x, int64_t n,
                                             uint8_t* __restrict__ codes, int bits, uint32_t* __restrict__ stage) {
     const int lane = threadIdx.x & 63;
     const int64_t nwaves_total = (int64_t)gridDim.x * (kQThreads / 64);
     const int64_t wave_id = (int64_t)blockIdx.x * (kQThreads / 64) + (threadIdx.x >> 6);
     const int64_t full_tiles = n / 1024;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (is_lowp<X>::value) {
+        // software-pipelined like the fp32 form: the next tile's 2 KiB is in flight while this one is binned
+        u32x4_v f[2];
+        if (wave_id < full_tiles) {
+            const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + wave_id * 1024);
+#pragma unroll
+            for (int j = 0; j < 2; j++) f[j] = __builtin_nontemporal_load(src + j * 64 + lane);
+        }
+        const bool wt = SKML_Q_STORE != 0 && bits == 8 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0;
+        const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
+            codes, 0, (int)std::min<int64_t>(full_tiles * 1024, (int64_t)0x7FFFFC00), 0x00020000);
+        for (int64_t tile = wave_id; tile < full_tiles; tile += nwaves_total) {
+            u32x4_v g[2];
+            const int64_t next = tile + nwaves_total;
+            if (next < full_tiles) {
+                const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + next * 1024);
+#pragma unroll
+                for (int j = 0; j < 2; j++) g[j] = __builtin_nontemporal_load(src + j * 64 + lane);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                float v[8];
+                widen8<X>(f[j], v);
+                uint32_t c[8];
+#pragma unroll
+                for (int e = 0; e < 8; e++) c[e] = quant_bin<MODE>(q, v[e]);
+                if (wt) {  // codes j * 512 + lane * 8 .. + 7 of the tile: two words of the stage
+                    reinterpret_cast<uint2*>(stage)[j * 64 + lane] = make_uint2(
+                        c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24));
+                } else {
+                    store_codes8(codes, tile * 1024 + j * 512 + lane * 8, c, bits);
+                }
+            }
+            if (wt) {
+                __builtin_amdgcn_wave_barrier();
+                const uint4 w = reinterpret_cast<const uint4*>(stage)[lane];
+                __builtin_amdgcn_wave_barrier();  // the stage is read before the next tile overwrites it
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4_v{w.x, w.y, w.z, w.w}, crs, (int)(tile * 1024 + lane * 16), 0,
+                                                       SKML_Q_STORE == 2 ? 16 /* sc1: write-through */ : 2 /* nt */);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; j++) f[j] = g[j];
+        }
+    } else {
     // software-pipelined: the next tile's 4 KiB is in flight while this one is binned
     f32x4 f[4];
     if (wave_id < full_tiles) {
@@ -152,6 +228,7 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const float* _
 #pragma unroll
         for (int j = 0; j < 4; j++) f[j] = g[j];
     }
+    }
     // tail tile (n % 1024 values), one wave, guarded element loads
     if (wave_id == full_tiles % nwaves_total && n % 1024) {
         const int64_t base = full_tiles * 1024;
@@ -160,7 +237,7 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const float* _
             const int64_t e0 = base + j * 256 + lane * 4;
             uint32_t c[4] = {0, 0, 0, 0};
             for (int e = 0; e < 4; e++)
-                if (e0 + e < n) c[e] = quant_bin<MODE>(q, x[e0 + e]);
+                if (e0 + e < n) c[e] = quant_bin<MODE>(q, load_widen(x, e0 + e));
             if (bits == 1) {
                 const int64_t pair0 = base + j * 256 + (lane & ~1) * 4;
                 const uint32_t nib = c[0] | (c[1] << 1) | (c[2] << 2) | (c[3] << 3);
@@ -175,7 +252,8 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const float* _
 
 // Dynamic LDS: [0, 32 KB) bucket bases, then `lds_splits` floats (LUT mode); Eytzinger mode
 // reuses the start of the same buffer (P <= 4096 floats).
-__global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_quantize(const float* __restrict__ x, int64_t n,
+template <typename X = float>
+__global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_quantize(const X* __restrict__ x, int64_t n,
                                                         uint8_t* __restrict__ payload,
                                                         const QuantLut* __restrict__ lut, int lds_splits) {
     extern __shared__ __align__(16) uint8_t qsm[];
@@ -244,16 +322,30 @@ static int quant_grid(int64_t n) {
     return (int)wg;
 }
 
-hipError_t launch_quantize(hipStream_t st, const float* x, int64_t n, void* payload, const QuantLut* lut,
-                           int req_bins) {
+hipError_t launch_quantize(hipStream_t st, const void* x, int64_t n, void* payload, const QuantLut* lut,
+                           int req_bins, int xtype) {
     if (n <= 0) return hipSuccess;
     // LDS sized for this request's split table; persistent-style grid (the LUT is loaded once per WG)
     const int lds_splits = std::min(std::max(req_bins - 1, 1), kLutMaxSplits) + kLutPad;
     const size_t lds = sizeof(QuantLut::base) + (size_t)lds_splits * sizeof(float);
     const int64_t tiles = (n + 1023) / 1024;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, SKML_Q_GRID));
-    hipLaunchKernelGGL(k_quantize, dim3(grid), dim3(kQThreads), lds, st, x, n,
-                       reinterpret_cast<uint8_t*>(payload), lut, lds_splits);
+    uint8_t* pl = reinterpret_cast<uint8_t*>(payload);
+    switch (xtype) {
+        case kXF32:
+            hipLaunchKernelGGL(k_quantize<float>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const float*>(x), n, pl,
+                               lut, lds_splits);
+            break;
+        case kXBF16:
+            hipLaunchKernelGGL(k_quantize<bf16_t>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const bf16_t*>(x), n,
+                               pl, lut, lds_splits);
+            break;
+        case kXF16:
+            hipLaunchKernelGGL(k_quantize<f16_t>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const f16_t*>(x), n, pl,
+                               lut, lds_splits);
+            break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
@@ -310,8 +402,12 @@ __device__ __forceinline__ double lut_value(const skml_dense_header* h, const do
 
 constexpr int kLutMax = 4096;
 
+// O: the output's storage type.  A 16-bit output is the float result rounded to nearest even; it
+// leaves as 16-byte nontemporal stores (8 values per lane) when `out` is 16-byte aligned and as
+// element stores otherwise.
+template <typename O = float>
 __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ payload,
-                                                float* __restrict__ out, int64_t n) {
+                                                O* __restrict__ out, int64_t n) {
     __shared__ float lut[kLutMax];
     const skml_dense_header* h = reinterpret_cast<const skml_dense_header*>(payload);
     const double* sp = reinterpret_cast<const double*>(payload + kHeaderBytes);
@@ -326,6 +422,30 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ payl
     const int64_t nw = (int64_t)gridDim.x * 4, wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t full = n / 1024;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (is_lowp<O>::value) {
+        auto value = [&](uint32_t c) -> float { return lds ? lut[c] : (float)lut_value(h, sp, (int)c); };
+        if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) {  // element path
+            for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+                store_narrow(out, e, value(read_code(codes, e, bits)));
+            return;
+        }
+        for (int64_t tile = wid; tile < full; tile += nw) {
+            uint32_t c[2][2][4];
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                read_codes4(codes, tile * 1024 + j * 512 + lane * 8, bits, c[j][0]);
+                read_codes4(codes, tile * 1024 + j * 512 + lane * 8 + 4, bits, c[j][1]);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const float v[8] = {value(c[j][0][0]), value(c[j][0][1]), value(c[j][0][2]), value(c[j][0][3]),
+                                    value(c[j][1][0]), value(c[j][1][1]), value(c[j][1][2]), value(c[j][1][3])};
+                store_narrow8(out, tile * 1024 + j * 512 + lane * 8, v);
+            }
+        }
+        if (wid == full % nw)
+            for (int64_t e = full * 1024 + lane; e < n; e += 64) store_narrow(out, e, value(read_code(codes, e, bits)));
+    } else {
     for (int64_t tile = wid; tile < full; tile += nw) {
         f32x4* dst = reinterpret_cast<f32x4*>(out + tile * 1024);
         uint32_t c[4][4];
@@ -347,12 +467,18 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ payl
             out[e] = lds ? lut[c] : (float)lut_value(h, sp, c);
         }
     }
+    }
 }
 
-hipError_t launch_decode(hipStream_t st, const void* payload, float* out, int64_t n) {
+hipError_t launch_decode(hipStream_t st, const void* payload, void* out, int64_t n, int otype) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_decode, dim3(quant_grid(n)), dim3(256), 0, st,
-                       reinterpret_cast<const uint8_t*>(payload), out, n);
+    const uint8_t* pl = reinterpret_cast<const uint8_t*>(payload);
+    switch (otype) {
+        case kXF32: hipLaunchKernelGGL(k_decode<float>, dim3(quant_grid(n)), dim3(256), 0, st, pl, static_cast<float*>(out), n); break;
+        case kXBF16: hipLaunchKernelGGL(k_decode<bf16_t>, dim3(quant_grid(n)), dim3(256), 0, st, pl, static_cast<bf16_t*>(out), n); break;
+        case kXF16: hipLaunchKernelGGL(k_decode<f16_t>, dim3(quant_grid(n)), dim3(256), 0, st, pl, static_cast<f16_t*>(out), n); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
@@ -401,9 +527,29 @@ __device__ __forceinline__ uint32_t code16_at(const uint32_t (&w)[8], int e, int
 // likewise, and stores 64 contiguous bytes of fp32 (nontemporal).  BITS: the code width when all
 // payloads share it (the common case: one bin count), 0 = per payload.
 constexpr int kSumChunk = 8;
-template <int BITS>
+// A lane's N (8 or 16) sums as 16-bit values: (float)(acc * scale) as in the fp32 form, rounded to
+// nearest even; one or two 16-byte nontemporal stores (vec: `out` is 16-byte aligned), element
+// stores otherwise.
+template <typename O, int N>
+__device__ __forceinline__ void store_sum_lowp(O* __restrict__ out, int64_t e0, const double (&acc)[N], double scale,
+                                               bool vec) {
+#pragma unroll
+    for (int h = 0; h < N / 8; h++) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = (float)(acc[8 * h + k] * scale);
+        if (vec) {
+            store_narrow8(out, e0 + 8 * h, v);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) store_narrow(out, e0 + 8 * h + k, v[k]);
+        }
+    }
+}
+// O: the output's storage type (the final store only; the sum is the fp32 form's).
+template <int BITS, typename O = float>
 __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ payloads, int P,
-                                                    size_t stride, float* __restrict__ out, int64_t n,
+                                                    size_t stride, O* __restrict__ out, int64_t n,
                                                     double scale) {
     __shared__ double lut[kMaxSumPayloads][kSumLutBins];
     __shared__ const uint8_t* s_codes[kMaxSumPayloads];
@@ -433,6 +579,7 @@ __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ 
     const int64_t full = n / 16;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int64_t gstep = (int64_t)gridDim.x * 256;
+    [[maybe_unused]] const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     if (BITS && P <= kSumChunk) {
         // software-pipelined: the next step's code loads are issued before this step's lookups, so
         // a wave waits on HBM once per kernel instead of once per step
@@ -462,12 +609,16 @@ __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ 
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc[e] += value(q, code16_at(w[q], e, BITS));
             }
+            if constexpr (is_lowp<O>::value) {
+                store_sum_lowp(out, g * 16, acc, scale, vec);
+            } else {
             f32x4* dst = reinterpret_cast<f32x4*>(out + g * 16);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const f32x4 o = {(float)(acc[4 * j] * scale), (float)(acc[4 * j + 1] * scale),
                                  (float)(acc[4 * j + 2] * scale), (float)(acc[4 * j + 3] * scale)};
                 __builtin_nontemporal_store(o, dst + j);
+            }
             }
         }
     } else
@@ -491,6 +642,9 @@ __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ 
                 for (int e = 0; e < 16; e++) acc[e] += value(p0 + q, code16_at(w[q], e, bits));
             }
         }
+        if constexpr (is_lowp<O>::value) {
+            store_sum_lowp(out, e0, acc, scale, vec);
+        } else {
         f32x4* dst = reinterpret_cast<f32x4*>(out + e0);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -498,13 +652,14 @@ __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ 
                              (float)(acc[4 * j + 2] * scale), (float)(acc[4 * j + 3] * scale)};
             __builtin_nontemporal_store(o, dst + j);
         }
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x < 16) {  // the last n % 16 elements
         const int64_t e = full * 16 + threadIdx.x;
         if (e < n) {
             double a = 0.0;
             for (int p = 0; p < P; p++) a += value(p, read_code(s_codes[p], e, s_bits[p]));
-            out[e] = (float)(a * scale);
+            store_narrow(out, e, (float)(a * scale));
         }
     }
 }
@@ -569,9 +724,9 @@ template <int BITS>
 __device__ __forceinline__ uint32_t code_occ_at(const uint32_t (&w)[occ_words<BITS>()], int e) {
     return (w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u);
 }
-template <int BITS, bool PF>
+template <int BITS, bool PF, typename O = float>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF ? (BITS >= 8 ? SKML_OCC_WAVES : SKML_OCC_WAVES_NARROW) : 8))) void k_decode_sum_occ(
-    const uint8_t* __restrict__ payloads, int P, size_t stride, float* __restrict__ out, int64_t n, double scale,
+    const uint8_t* __restrict__ payloads, int P, size_t stride, O* __restrict__ out, int64_t n, double scale,
     int tab) {
     extern __shared__ double lt[];  // P tables of `tab` doubles
     __shared__ const uint8_t* s_codes[kOccMaxP];
@@ -620,6 +775,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF ? (BITS 
 #pragma unroll
             for (int e = 0; e < kOccPer; e++) acc[e] += t[code_occ_at<BITS>(w[q], e)];
         }
+        if constexpr (is_lowp<O>::value) {
+            store_sum_lowp(out, g * kOccPer, acc, scale, (reinterpret_cast<uintptr_t>(out) & 15) == 0);
+        } else {
         f32x4* dst = reinterpret_cast<f32x4*>(out + g * kOccPer);
 #pragma unroll
         for (int j = 0; j < kOccPer / 4; j++) {
@@ -627,37 +785,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF ? (BITS 
                              (float)(acc[4 * j + 2] * scale), (float)(acc[4 * j + 3] * scale)};
             __builtin_nontemporal_store(o, dst + j);
         }
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x < kOccPer) {  // the last n % kOccPer elements
         const int64_t e = full * kOccPer + threadIdx.x;
         if (e < n) {
             double a = 0.0;
             for (int p = 0; p < P; p++) a += lt[p * tab + read_code(s_codes[p], e, BITS)];
-            out[e] = (float)(a * scale);
+            store_narrow(out, e, (float)(a * scale));
         }
     }
 }
 
-template <int BITS>
-hipError_t launch_occ(hipStream_t st, const uint8_t* pl, int P, size_t stride, float* out, int64_t n, double scale,
+template <int BITS, typename O>
+hipError_t launch_occ(hipStream_t st, const uint8_t* pl, int P, size_t stride, O* out, int64_t n, double scale,
                       int max_bins) {
     const size_t lds = sizeof(double) * (size_t)max_bins * (size_t)P;
     const int64_t groups = n / kOccPer;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 4096));
 #ifdef SKML_AB
     if (form(SKML_FORM_DECODE_SUM) == 2) {  // A/B: without the next step's prefetch (slower)
-        hipLaunchKernelGGL((k_decode_sum_occ<BITS, false>), dim3(grid), dim3(256), lds, st, pl, P, stride, out, n, scale,
+        hipLaunchKernelGGL((k_decode_sum_occ<BITS, false, O>), dim3(grid), dim3(256), lds, st, pl, P, stride, out, n, scale,
                            max_bins);
         return hipGetLastError();
     }
 #endif
-    hipLaunchKernelGGL((k_decode_sum_occ<BITS, true>), dim3(grid), dim3(256), lds, st, pl, P, stride, out, n, scale,
+    hipLaunchKernelGGL((k_decode_sum_occ<BITS, true, O>), dim3(grid), dim3(256), lds, st, pl, P, stride, out, n, scale,
                        max_bins);
     return hipGetLastError();
 }
 
-hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, float* out,
-                             int64_t n, double scale, int common_bits, int max_bins) {
+template <typename O>
+static hipError_t launch_decode_sum_o(hipStream_t st, const void* payloads, int P, size_t stride, O* out,
+                                      int64_t n, double scale, int common_bits, int max_bins) {
     if (n <= 0) return hipSuccess;
     if (P < 1 || P > kMaxSumPayloads) return hipErrorInvalidValue;
     // the occupancy form whenever the P tables fit beside its static LDS: every 1..8-bit shape
@@ -665,11 +825,11 @@ hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t
     if ((size_t)max_bins * (size_t)P * sizeof(double) <= kOccLdsMax && P <= kOccMaxP && form(SKML_FORM_DECODE_SUM) != 1) {
         const uint8_t* pl = reinterpret_cast<const uint8_t*>(payloads);
         switch (common_bits) {
-            case 16: return launch_occ<16>(st, pl, P, stride, out, n, scale, max_bins);
-            case 8: return launch_occ<8>(st, pl, P, stride, out, n, scale, max_bins);
-            case 4: return launch_occ<4>(st, pl, P, stride, out, n, scale, max_bins);
-            case 2: return launch_occ<2>(st, pl, P, stride, out, n, scale, max_bins);
-            case 1: return launch_occ<1>(st, pl, P, stride, out, n, scale, max_bins);
+            case 16: return launch_occ<16, O>(st, pl, P, stride, out, n, scale, max_bins);
+            case 8: return launch_occ<8, O>(st, pl, P, stride, out, n, scale, max_bins);
+            case 4: return launch_occ<4, O>(st, pl, P, stride, out, n, scale, max_bins);
+            case 2: return launch_occ<2, O>(st, pl, P, stride, out, n, scale, max_bins);
+            case 1: return launch_occ<1, O>(st, pl, P, stride, out, n, scale, max_bins);
             default: break;  // mixed widths: the per-payload kernel below
         }
     }
@@ -677,13 +837,23 @@ hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 2048));
     const uint8_t* pl = reinterpret_cast<const uint8_t*>(payloads);
     switch (common_bits) {
-        case 8: hipLaunchKernelGGL(k_decode_sum<8>, dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
-        case 2: hipLaunchKernelGGL(k_decode_sum<2>, dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
-        case 4: hipLaunchKernelGGL(k_decode_sum<4>, dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
-        case 1: hipLaunchKernelGGL(k_decode_sum<1>, dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
-        default: hipLaunchKernelGGL(k_decode_sum<0>, dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
+        case 8: hipLaunchKernelGGL((k_decode_sum<8, O>), dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
+        case 2: hipLaunchKernelGGL((k_decode_sum<2, O>), dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
+        case 4: hipLaunchKernelGGL((k_decode_sum<4, O>), dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
+        case 1: hipLaunchKernelGGL((k_decode_sum<1, O>), dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
+        default: hipLaunchKernelGGL((k_decode_sum<0, O>), dim3(grid), dim3(256), 0, st, pl, P, stride, out, n, scale); break;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, void* out,
+                             int64_t n, double scale, int common_bits, int max_bins, int otype) {
+    switch (otype) {
+        case kXF32: return launch_decode_sum_o(st, payloads, P, stride, static_cast<float*>(out), n, scale, common_bits, max_bins);
+        case kXBF16: return launch_decode_sum_o(st, payloads, P, stride, static_cast<bf16_t*>(out), n, scale, common_bits, max_bins);
+        case kXF16: return launch_decode_sum_o(st, payloads, P, stride, static_cast<f16_t*>(out), n, scale, common_bits, max_bins);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // getBins(): int32 bins

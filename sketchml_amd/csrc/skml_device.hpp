@@ -22,6 +22,70 @@ __device__ __forceinline__ uint32_t key2f(uint32_t k) {
 __device__ __forceinline__ bool is_nan_bits(uint32_t b) { return (b & 0x7FFFFFFFu) > 0x7F800000u; }
 
 // ------------------------------------------------------------------------------------------
+// 16-bit storage (bf16_t / f16_t, skml_internal.h).  Widening is exact for every bit pattern: a
+// shift or a mask for bf16, v_cvt_f32_f16 for fp16.  Narrowing rounds the float to nearest even
+// (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).
+// ------------------------------------------------------------------------------------------
+typedef _Float16 f16x2_v __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_v __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_v __attribute__((ext_vector_type(4)));
+template <typename X>
+struct is_lowp : std::integral_constant<bool, std::is_same<X, bf16_t>::value || std::is_same<X, f16_t>::value> {};
+
+// One element x[i].
+template <typename X>
+__device__ __forceinline__ float load_widen(const X* __restrict__ x, int64_t i) {
+    if constexpr (std::is_same<X, bf16_t>::value) return __uint_as_float((uint32_t)x[i].bits << 16);
+    else if constexpr (std::is_same<X, f16_t>::value) return (float)__builtin_bit_cast(_Float16, x[i].bits);
+    else return x[i];
+}
+// The two 16-bit values of one word, low half first.
+template <typename X>
+__device__ __forceinline__ void widen2(uint32_t w, float& lo, float& hi) {
+    static_assert(is_lowp<X>::value, "16-bit storage only");
+    if constexpr (std::is_same<X, bf16_t>::value) {
+        lo = __uint_as_float(w << 16);
+        hi = __uint_as_float(w & 0xFFFF0000u);
+    } else {
+        const f16x2_v h = __builtin_bit_cast(f16x2_v, w);
+        lo = (float)h.x;
+        hi = (float)h.y;
+    }
+}
+// The 8 values of one 16-byte load into v[0..8).
+template <typename X>
+__device__ __forceinline__ void widen8(const u32x4_v& w, float* v) {
+    widen2<X>(w.x, v[0], v[1]);
+    widen2<X>(w.y, v[2], v[3]);
+    widen2<X>(w.z, v[4], v[5]);
+    widen2<X>(w.w, v[6], v[7]);
+}
+template <typename O>
+__device__ __forceinline__ uint32_t narrow2(float lo, float hi) {
+    static_assert(is_lowp<O>::value, "16-bit storage only");
+    if constexpr (std::is_same<O, bf16_t>::value) {
+        const bf16x2_v r = {(__bf16)lo, (__bf16)hi};
+        return __builtin_bit_cast(uint32_t, r);
+    } else {
+        const f16x2_v r = {(_Float16)lo, (_Float16)hi};
+        return __builtin_bit_cast(uint32_t, r);
+    }
+}
+// out[i] = v in O's format (float: as is).
+template <typename O>
+__device__ __forceinline__ void store_narrow(O* __restrict__ out, int64_t i, float v) {
+    if constexpr (std::is_same<O, bf16_t>::value) out[i].bits = __builtin_bit_cast(uint16_t, (__bf16)v);
+    else if constexpr (std::is_same<O, f16_t>::value) out[i].bits = __builtin_bit_cast(uint16_t, (_Float16)v);
+    else out[i] = v;
+}
+// 8 consecutive 16-bit results as one 16-byte nontemporal store (out + i 16-byte aligned).
+template <typename O>
+__device__ __forceinline__ void store_narrow8(O* __restrict__ out, int64_t i, const float (&v)[8]) {
+    const u32x4_v o = {narrow2<O>(v[0], v[1]), narrow2<O>(v[2], v[3]), narrow2<O>(v[4], v[5]), narrow2<O>(v[6], v[7])};
+    __builtin_nontemporal_store(o, reinterpret_cast<u32x4_v*>(out + i));
+}
+
+// ------------------------------------------------------------------------------------------
 // Cross-lane exchange: value held by lane ^ M.  Picks the cheapest gfx950 primitive per mask:
 // DPP quad_perm / row_mirror / row_half_mirror / row_ror:8 when the pattern stays inside a
 // 16-lane row, ds_swizzle (bit mode) inside 32 lanes, ds_bpermute otherwise.

@@ -11,6 +11,13 @@ namespace skml {
 // The kernel form selected by skml_debug_form (SKML_FORM_*): 0 = the library's own choice.
 int form(int id);
 
+// Storage type of a dense input or output buffer.  The sketch sorts and merges float whatever the
+// storage: bf16 and fp16 widen to float exactly, so a 16-bit encode is the fp32 encode of the
+// widened buffer, byte for byte.
+enum XType : int { kXF32 = 0, kXBF16 = 1, kXF16 = 2 };
+struct bf16_t { uint16_t bits; };
+struct f16_t { uint16_t bits; };
+
 constexpr uint64_t kLcgMult = 0x5DEECE66DULL;  // java.util.Random
 constexpr uint64_t kLcgAdd = 0xBULL;
 constexpr uint64_t kLcgMask = (1ULL << 48) - 1;
@@ -131,8 +138,11 @@ __host__ __device__ inline int64_t upper_node_count(int64_t C) { return upper_le
 
 // ---- kernel launchers (skml_sketch.hip) ----
 // ubits: upper_node_count(full tiles * 64) bytes; the leaf draws the upper merge tree's bits into it
-hipError_t launch_leaf(hipStream_t st, const float* x, int64_t chunks, uint64_t s0,
-                       const uint64_t* jump_tab, LeafPartial* part, float* nodes6, float* roots, uint8_t* ubits);
+// x: `chunks` x 256 values of storage type xtype (launch_leaf, launch_merge_pass, launch_summary
+// and launch_quantize alike)
+hipError_t launch_leaf(hipStream_t st, const void* x, int64_t chunks, uint64_t s0,
+                       const uint64_t* jump_tab, LeafPartial* part, float* nodes6, float* roots, uint8_t* ubits,
+                       int xtype = kXF32);
 hipError_t launch_leaf_stage(hipStream_t st, int stage, const float* x, int64_t chunks, uint64_t s0,
                              const uint64_t* jump_tab, LeafPartial* part, float* scratch, float* roots);
 // fp64 merge pass over double nodes (no summary; `next` as in launch_merge_pass).
@@ -154,25 +164,27 @@ hipError_t launch_sketch_merge(hipStream_t st, const SketchRecord* recs, int nre
 // its output `next_dst`), saving a launch.
 hipError_t launch_merge_pass(hipStream_t st, const MergePass& pass, const MergePass* next, const float* src,
                              float* dst, float* next_dst, float* roots, uint64_t s0, const uint64_t* jump_tab,
-                             unsigned* done, const float* x, int64_t n, const LeafPartial* part, int64_t nparts,
+                             unsigned* done, const void* x, int64_t n, const LeafPartial* part, int64_t nparts,
                              const int64_t* ranks, int req_bins, int dedup, void* payload,
                              double* scratch_raw, QuantLut* lut, const uint8_t* ubits, LeafPartial* part_red,
-                             int64_t nred, int64_t part_from);
-hipError_t launch_summary(hipStream_t st, const float* x, int64_t n, const LeafPartial* part,
+                             int64_t nred, int64_t part_from, int xtype = kXF32);
+hipError_t launch_summary(hipStream_t st, const void* x, int64_t n, const LeafPartial* part,
                           int64_t nparts, const float* roots, const int64_t* ranks, int req_bins,
-                          int dedup, void* payload, double* scratch_raw, QuantLut* lut);
+                          int dedup, void* payload, double* scratch_raw, QuantLut* lut, int xtype = kXF32);
 // getQuantiles' rank table for (n, bins) written on the device (bins - 1 int64)
 hipError_t launch_set_ranks(hipStream_t st, int64_t n, int bins, int64_t* ranks);
 hipError_t launch_set_splits(hipStream_t st, void* payload, int64_t n, const double* splits_dev,
                              int nsplits, double mn, double mx, int req_bins, QuantLut* lut);
 // ---- kernel launchers (skml_dense.hip) ----
 // `lut` may be null (Eytzinger / global search); req_bins sizes the kernel's LDS split table.
-hipError_t launch_quantize(hipStream_t st, const float* x, int64_t n, void* payload, const QuantLut* lut,
-                           int req_bins);
-hipError_t launch_decode(hipStream_t st, const void* payload, float* out, int64_t n);
-hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, float* out,
+hipError_t launch_quantize(hipStream_t st, const void* x, int64_t n, void* payload, const QuantLut* lut,
+                           int req_bins, int xtype = kXF32);
+// out: n values of storage type otype; a 16-bit `out` needs 2-byte alignment only (16-byte stores
+// when it is 16-byte aligned, element stores otherwise), a float `out` 16-byte alignment
+hipError_t launch_decode(hipStream_t st, const void* payload, void* out, int64_t n, int otype = kXF32);
+hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, void* out,
                              int64_t n, double scale, int common_bits,
-                             int max_bins);  // common_bits 0: mixed widths
+                             int max_bins, int otype = kXF32);  // common_bits 0: mixed widths
 hipError_t launch_bins(hipStream_t st, const void* payload, int32_t* bins, int64_t n);
 hipError_t launch_ref_body(hipStream_t st, const void* payload, uint8_t* out, int64_t n, int width);
 hipError_t launch_times_by(hipStream_t st, void* payload, double x);

@@ -335,8 +335,9 @@ __device__ __forceinline__ uint32_t fold32(double d) {
     return (uint32_t)b ^ (uint32_t)(b >> 32);
 }
 
-template <int STAGE, bool PARTIAL = false, typename E = float>
-__device__ __forceinline__ void leaf2_wave(const E* __restrict__ x, int64_t chunks, uint64_t s0,
+// X: the storage type of x (E itself, or bf16_t / f16_t widened to E = float by the loader).
+template <int STAGE, bool PARTIAL = false, typename E = float, typename X = E>
+__device__ __forceinline__ void leaf2_wave(const X* __restrict__ x, int64_t chunks, uint64_t s0,
                                            const uint64_t* __restrict__ tab,
                                            typename LeafTypes<E>::Part* __restrict__ part, E* __restrict__ nodes6,
                                            E* __restrict__ roots, int64_t tile, uint8_t* __restrict__ ubits,
@@ -383,6 +384,19 @@ __device__ __forceinline__ void leaf2_wave(const E* __restrict__ x, int64_t chun
                 zmask |= __ballot(is_class(f[j].x, 0x63) || is_class(f[j].y, 0x63));  // -0.0 | +0.0 | NaN
                 v[2 * j] = f[j].x;
                 v[2 * j + 1] = f[j].y;
+            }
+        } else if constexpr (is_lowp<X>::value) {
+            // a chunk is 512 B: 4 x 16 B (8 values each) per lane; any assignment of the chunk's
+            // values to its 8 lanes does, the chunk is sorted next
+            const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + (valid ? chunk : c0) * kChunk);
+            u32x4_v f[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) f[j] = src[j * 8 + (lane & 7)];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                widen8<X>(f[j], v + j * 8);
+#pragma unroll
+                for (int e = 0; e < 8; e++) zmask |= __ballot(is_class(v[j * 8 + e], 0x63));  // -0.0 | +0.0 | NaN
             }
         } else {
             const float4* src = reinterpret_cast<const float4*>(x + (valid ? chunk : c0) * kChunk);
@@ -544,14 +558,14 @@ __device__ __forceinline__ void leaf2_wave(const E* __restrict__ x, int64_t chun
     }
 }
 
-template <int STAGE, bool PARTIAL = false, typename E = float>
+template <int STAGE, bool PARTIAL = false, typename E = float, typename X = E>
 __global__ __launch_bounds__(256, LeafTypes<E>::kMinWaves) void k_leaf2(
-    const E* __restrict__ x, int64_t chunks, uint64_t s0, const uint64_t* __restrict__ tab,
+    const X* __restrict__ x, int64_t chunks, uint64_t s0, const uint64_t* __restrict__ tab,
     typename LeafTypes<E>::Part* __restrict__ part, E* __restrict__ nodes6, E* __restrict__ roots, int64_t tile0,
     uint8_t* __restrict__ ubits = nullptr) {
     __shared__ E fb[kLeaf2Waves][kWaveFb];
     const int wave = threadIdx.x >> 6;
-    leaf2_wave<STAGE, PARTIAL, E>(x, chunks, s0, tab, part, nodes6, roots,
+    leaf2_wave<STAGE, PARTIAL, E, X>(x, chunks, s0, tab, part, nodes6, roots,
                                   tile0 + (int64_t)blockIdx.x * kLeaf2Waves + wave, ubits, fb[wave]);
 }
 
@@ -586,8 +600,8 @@ struct Leaf64Shared {
     float2 stk[kLeaf2Waves][2][64];  // the carry stack (levels 4, 5) in LDS, not registers
     uint32_t wpart[kLeaf2Waves][4];  // SPLIT: each wave's min / max / flags / zero signs
 };
-template <bool SPLIT>
-__device__ __forceinline__ void leaf64_tile(const float* __restrict__ x, int64_t chunks, uint64_t s0,
+template <bool SPLIT, typename X = float>
+__device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chunks, uint64_t s0,
                                             const uint64_t* __restrict__ tab, LeafPartial* __restrict__ part,
                                             float* __restrict__ nodes6, float* __restrict__ roots,
                                             uint8_t* __restrict__ ubits, int64_t tile, Leaf64Shared& L) {
@@ -619,7 +633,31 @@ __device__ __forceinline__ void leaf64_tile(const float* __restrict__ x, int64_t
             const int64_t chunk = c0 + (ln >> 2);
             float v[64];
             uint64_t zmask = 0;
-            {
+            if constexpr (is_lowp<X>::value) {
+                // a chunk is 512 B: 8 x 16 B (8 values each) per lane in place of 16 float4; any
+                // assignment of the chunk's values to its 4 lanes does, the chunk is sorted next
+                const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + chunk * kChunk);
+                u32x4_v f[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) f[j] = src[j * kL64Lanes + (ln & 3)];
+#pragma unroll
+                for (int j = 0; j < 8; j++) widen8<X>(f[j], v + j * 8);
+                // the zero / NaN detector of the fp32 form below, on the widened values
+#if SKML_LEAF_MIN3DET
+                float za = __builtin_inff(), zb = __builtin_inff();
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    asm("v_minimum3_f32 %0, |%1|, |%2|, %3" : "=v"(za) : "v"(v[j * 4 + 0]), "v"(v[j * 4 + 1]), "v"(za));
+                    asm("v_minimum3_f32 %0, |%1|, |%2|, %3" : "=v"(zb) : "v"(v[j * 4 + 2]), "v"(v[j * 4 + 3]), "v"(zb));
+                }
+                float zm;
+                asm("v_minimum3_f32 %0, %1, %2, %2" : "=v"(zm) : "v"(za), "v"(zb));
+                zmask = __ballot(!(zm > 0.0f));
+#else
+#pragma unroll
+                for (int r = 0; r < 64; r++) zmask |= __ballot(is_class(v[r], 0x63));  // -0.0 | +0.0 | NaN
+#endif
+            } else {
                 const float4* src = reinterpret_cast<const float4*>(x + chunk * kChunk);
                 float4 f[16];
 #pragma unroll
@@ -823,8 +861,8 @@ __device__ __forceinline__ void leaf64_tile(const float* __restrict__ x, int64_t
 // the end of a large bucket runs in quarter-size units: one wave per tile left a tail in which
 // the chip ran short of waves (2^28: wave-slot use 0.82 over the span, tools/prof_leaf_waves.py,
 // profiles/r05d_leaf_waves.txt).
-template <int MODE>
-__global__ __launch_bounds__(256, SKML_LEAF64_WAVES) void k_leaf64(const float* __restrict__ x, int64_t chunks, uint64_t s0,
+template <int MODE, typename X = float>
+__global__ __launch_bounds__(256, SKML_LEAF64_WAVES) void k_leaf64(const X* __restrict__ x, int64_t chunks, uint64_t s0,
                                                    const uint64_t* __restrict__ tab, LeafPartial* __restrict__ part,
                                                    float* __restrict__ nodes6, float* __restrict__ roots,
                                                    uint8_t* __restrict__ ubits, int64_t total_chunks,
@@ -835,20 +873,20 @@ __global__ __launch_bounds__(256, SKML_LEAF64_WAVES) void k_leaf64(const float* 
     if (total_chunks > chunks) {
         if (blk == 0) {
             if (wave == 0)
-                leaf2_wave<3, true, float>(x, total_chunks, s0, tab, part, nodes6, roots, chunks / kLeafWaveChunks,
+                leaf2_wave<3, true, float, X>(x, total_chunks, s0, tab, part, nodes6, roots, chunks / kLeafWaveChunks,
                                            nullptr, L.fb[0]);
             return;
         }
         blk -= 1;
     }
     if constexpr (MODE == 0) {
-        leaf64_tile<false>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk * kLeaf2Waves + wave, L);
+        leaf64_tile<false, X>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk * kLeaf2Waves + wave, L);
     } else if constexpr (MODE == 1) {
-        leaf64_tile<true>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk, L);
+        leaf64_tile<true, X>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk, L);
     } else {
         const int64_t nwg = split_from / kLeaf2Waves;  // split_from: a multiple of 4
-        if (blk < nwg) leaf64_tile<false>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk * kLeaf2Waves + wave, L);
-        else leaf64_tile<true>(x, chunks, s0, tab, part, nodes6, roots, ubits, split_from + (blk - nwg), L);
+        if (blk < nwg) leaf64_tile<false, X>(x, chunks, s0, tab, part, nodes6, roots, ubits, blk * kLeaf2Waves + wave, L);
+        else leaf64_tile<true, X>(x, chunks, s0, tab, part, nodes6, roots, ubits, split_from + (blk - nwg), L);
     }
 }
 
@@ -1051,8 +1089,9 @@ static int64_t leaf_split_from(int64_t full_tiles) {
 #endif
 }
 
-hipError_t launch_leaf(hipStream_t st, const float* x, int64_t chunks, uint64_t s0,
-                       const uint64_t* jump_tab, LeafPartial* part, float* nodes6, float* roots, uint8_t* ubits) {
+template <typename X>
+static hipError_t launch_leaf_x(hipStream_t st, const X* x, int64_t chunks, uint64_t s0,
+                                const uint64_t* jump_tab, LeafPartial* part, float* nodes6, float* roots, uint8_t* ubits) {
     const int64_t full = chunks / kLeafWaveChunks;
 #ifndef SKML_LEAF64
 #define SKML_LEAF64 1
@@ -1061,32 +1100,42 @@ hipError_t launch_leaf(hipStream_t st, const float* x, int64_t chunks, uint64_t 
         const int extra = chunks % kLeafWaveChunks ? 1 : 0;
         const int64_t split_from = leaf_split_from(full);
         if (split_from == 0) {
-            hipLaunchKernelGGL(k_leaf64<1>, dim3((unsigned)(full + extra)), dim3(64 * kLeaf2Waves), 0, st, x,
+            hipLaunchKernelGGL((k_leaf64<1, X>), dim3((unsigned)(full + extra)), dim3(64 * kLeaf2Waves), 0, st, x,
                                full * kLeafWaveChunks, s0, jump_tab, part, nodes6, roots, ubits, chunks, (int64_t)0);
             return hipGetLastError();
         }
 #if defined(SKML_AB) || SKML_LEAF_SPLIT_TAIL_PCT < 100
         if (split_from >= full) {
             const unsigned grid = (unsigned)((full + kLeaf2Waves - 1) / kLeaf2Waves + extra);
-            hipLaunchKernelGGL(k_leaf64<0>, dim3(grid), dim3(64 * kLeaf2Waves), 0, st, x, full * kLeafWaveChunks, s0,
+            hipLaunchKernelGGL((k_leaf64<0, X>), dim3(grid), dim3(64 * kLeaf2Waves), 0, st, x, full * kLeafWaveChunks, s0,
                                jump_tab, part, nodes6, roots, ubits, chunks, full);
             return hipGetLastError();
         }
         const unsigned grid = (unsigned)(split_from / kLeaf2Waves + (full - split_from) + extra);
-        hipLaunchKernelGGL(k_leaf64<2>, dim3(grid), dim3(64 * kLeaf2Waves), 0, st, x, full * kLeafWaveChunks, s0,
+        hipLaunchKernelGGL((k_leaf64<2, X>), dim3(grid), dim3(64 * kLeaf2Waves), 0, st, x, full * kLeafWaveChunks, s0,
                            jump_tab, part, nodes6, roots, ubits, chunks, split_from);
         return hipGetLastError();
 #else
         return hipErrorInvalidValue;  // (unreachable: split_from is 0)
 #endif
     } else if (full > 0)
-        hipLaunchKernelGGL((k_leaf2<3, false>), dim3((unsigned)((full + kLeaf2Waves - 1) / kLeaf2Waves)),
+        hipLaunchKernelGGL((k_leaf2<3, false, float, X>), dim3((unsigned)((full + kLeaf2Waves - 1) / kLeaf2Waves)),
                            dim3(64 * kLeaf2Waves), 0, st, x, full * kLeafWaveChunks, s0, jump_tab, part,
                            nodes6, roots, (int64_t)0, ubits);
     if (chunks % kLeafWaveChunks)  // the small trees of the last chunks: one wave
-        hipLaunchKernelGGL((k_leaf2<3, true>), dim3(1), dim3(64), 0, st, x, chunks, s0, jump_tab, part,
+        hipLaunchKernelGGL((k_leaf2<3, true, float, X>), dim3(1), dim3(64), 0, st, x, chunks, s0, jump_tab, part,
                            nodes6, roots, full);
     return hipGetLastError();
+}
+
+hipError_t launch_leaf(hipStream_t st, const void* x, int64_t chunks, uint64_t s0, const uint64_t* jump_tab,
+                       LeafPartial* part, float* nodes6, float* roots, uint8_t* ubits, int xtype) {
+    switch (xtype) {
+        case kXF32: return launch_leaf_x(st, static_cast<const float*>(x), chunks, s0, jump_tab, part, nodes6, roots, ubits);
+        case kXBF16: return launch_leaf_x(st, static_cast<const bf16_t*>(x), chunks, s0, jump_tab, part, nodes6, roots, ubits);
+        case kXF16: return launch_leaf_x(st, static_cast<const f16_t*>(x), chunks, s0, jump_tab, part, nodes6, roots, ubits);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // fp64 leaf: the same wave-persistent kernel over doubles (level-6 nodes and roots as doubles).
@@ -1178,7 +1227,7 @@ __device__ int64_t block_scan_excl(int64_t v, int64_t* wsum, int64_t* total) {
 }
 
 struct SummaryArgs {
-    const float* x;
+    const void* x;  // storage type `xtype` (below)
     int64_t n;
     const LeafPartial* part;
     int64_t nparts;
@@ -1197,7 +1246,14 @@ struct SummaryArgs {
     const LeafPartial* part_red = nullptr;
     int64_t nred = 0;
     int64_t part_from = 0;
+    int xtype = kXF32;
 };
+// x[i] widened to float.
+__device__ __forceinline__ float load_widen_any(const void* x, int xtype, int64_t i) {
+    if (xtype == kXBF16) return load_widen(static_cast<const bf16_t*>(x), i);
+    if (xtype == kXF16) return load_widen(static_cast<const f16_t*>(x), i);
+    return static_cast<const float*>(x)[i];
+}
 
 // pre: this thread's min / max / flags of the leaf partials, already loaded by the caller (the
 // fused merge workgroup fetches them before its merge so the load latency hides there); null:
@@ -1212,7 +1268,10 @@ __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_p
     const int64_t n = a.n;
     const int64_t chunks = n / kChunk;
     const int tail = (int)(n - chunks * kChunk);
-    const float* xt = a.tail ? a.tail : a.x + chunks * kChunk;
+    // the base-buffer tail: a.tail (float), or the input's last n % 256 values in their storage type
+    const void* xt = a.tail ? (const void*)a.tail : a.x;
+    const int xt_type = a.tail ? (int)kXF32 : a.xtype;
+    const int64_t xt0 = a.tail ? 0 : chunks * kChunk;
     const int req_bins = a.req_bins;
     SKML_PROF(2);
 
@@ -1262,7 +1321,7 @@ __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_p
             }
         }
         for (int i = t; i < tail; i += T) {
-            const uint32_t b = __float_as_uint(xt[i]);
+            const uint32_t b = __float_as_uint(load_widen_any(xt, xt_type, xt0 + i));
             fl |= is_nan_bits(b) ? 1u : 0u;
             const uint32_t k = f2key(b);
             mn = k < mn ? k : mn;
@@ -1287,7 +1346,7 @@ __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_p
         const int r = idx / kK, i = idx % kK;
         S.smp[S.run_off[r] + i] = a.roots[(size_t)S.run_lvl[r] * kK + i];
     }
-    for (int i = t; i < tail; i += T) S.sorted[i] = xt[i];
+    for (int i = t; i < tail; i += T) S.sorted[i] = load_widen_any(xt, xt_type, xt0 + i);
     __syncthreads();
     {
         const int toff = S.run_off[nruns - 1];
@@ -1471,11 +1530,12 @@ __global__ __launch_bounds__(512) void k_summary(SummaryArgs a) {
     summary_block(a, S);
 }
 
-hipError_t launch_summary(hipStream_t st, const float* x, int64_t n, const LeafPartial* part,
+hipError_t launch_summary(hipStream_t st, const void* x, int64_t n, const LeafPartial* part,
                           int64_t nparts, const float* roots, const int64_t* ranks, int req_bins,
-                          int dedup, void* payload, double* scratch_raw, QuantLut* lut) {
+                          int dedup, void* payload, double* scratch_raw, QuantLut* lut, int xtype) {
     SummaryArgs a{x, n, part, nparts, roots, ranks, reinterpret_cast<uint8_t*>(payload), scratch_raw,
                   lut, req_bins, dedup};
+    a.xtype = xtype;
     hipLaunchKernelGGL(k_summary, dim3(1), dim3(512), 0, st, a);
     return hipGetLastError();
 }
@@ -1704,14 +1764,15 @@ __global__ __launch_bounds__(512) void k_merge(MergePass pass, MergePass next, c
 
 hipError_t launch_merge_pass(hipStream_t st, const MergePass& pass, const MergePass* next, const float* src,
                              float* dst, float* next_dst, float* roots, uint64_t s0, const uint64_t* jump_tab,
-                             unsigned* done, const float* x, int64_t n, const LeafPartial* part, int64_t nparts,
+                             unsigned* done, const void* x, int64_t n, const LeafPartial* part, int64_t nparts,
                              const int64_t* ranks, int req_bins, int dedup, void* payload,
                              double* scratch_raw, QuantLut* lut, const uint8_t* ubits, LeafPartial* part_red,
-                             int64_t nred, int64_t part_from) {
+                             int64_t nred, int64_t part_from, int xtype) {
     const int nwg = pass.wg_prefix[pass.njobs];
     if (nwg <= 0) return hipSuccess;
     SummaryArgs a{x, n, part, nparts, roots, ranks, reinterpret_cast<uint8_t*>(payload), scratch_raw,
                   lut, req_bins, dedup};
+    a.xtype = xtype;
     a.part_red = part_red;  // written by the first pass (this launch or an earlier one)
     a.nred = nred;
     a.part_from = part_from;

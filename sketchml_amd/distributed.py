@@ -21,7 +21,7 @@ import torch.distributed as dist
 import numpy as np
 
 from . import _lib
-from .context import as_device_values, get_context
+from .context import LOWP_DTYPES, as_device_f32, as_device_values, get_context
 from .exceptions import SketchMLException, check
 
 
@@ -144,9 +144,17 @@ def exchange_sparse(payload, dim: int, group=None, exchange: Optional[PayloadExc
 def decode_sum(ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, n: int, scale: float,
                out: torch.Tensor) -> None:
     """Fused decode of `nranks` gathered payloads + double-precision sum + scale
-    (Gradient.sum then timesBy(1/P), ml/gradient/Gradient.scala:44-49)."""
-    check(_lib.lib.skml_dense_decode_sum_f32(ctx_handle, C.c_void_p(payloads.data_ptr()), nranks, stride,
-                                             C.c_void_p(out.data_ptr()), n, float(scale)), "decode_sum")
+    (Gradient.sum then timesBy(1/P), ml/gradient/Gradient.scala:44-49) into `out`: fp32, or bf16 /
+    fp16 (the fp32 result rounded to nearest even by the kernel's final store)."""
+    fn = _DECODE_SUM.get(out.dtype)
+    if fn is None:
+        raise SketchMLException(f"decode_sum: unsupported output dtype {out.dtype}")
+    check(getattr(_lib.lib, fn)(ctx_handle, C.c_void_p(payloads.data_ptr()), nranks, stride,
+                                C.c_void_p(out.data_ptr()), n, float(scale)), "decode_sum")
+
+
+_DECODE_SUM = {torch.float32: "skml_dense_decode_sum_f32", torch.bfloat16: "skml_dense_decode_sum_bf16",
+               torch.float16: "skml_dense_decode_sum_f16"}
 
 
 # ---- one split table across ranks (SURVEY §8e single-split-table mode) ----------------------
@@ -167,6 +175,8 @@ def sketch_shard(values, shard_sizes, shard: int, seed: int = 0) -> torch.Tensor
     """This rank's slice sketch as a fixed-size device record (skml_dense_sketch_shard_f32 / _f64:
     fp64 values, the reference's double[], stay fp64)."""
     x = as_device_values(values)
+    if x.dtype in LOWP_DTYPES:
+        x = as_device_f32(x)  # the shard sketch has no 16-bit entry
     wide = x.dtype == torch.float64
     sizes = np.ascontiguousarray(shard_sizes, dtype=np.int64)
     rec = torch.empty(record_bytes(wide), dtype=torch.uint8, device=x.device)

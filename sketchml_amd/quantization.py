@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .constants import Parallel
-from .context import alloc_aligned, as_device_values, get_context
+from .context import LOWP_DTYPES, alloc_aligned, as_device_f32, as_device_values, get_context
 from .exceptions import QuantileSketchException, SketchMLException, check
 
 
@@ -94,6 +94,11 @@ class Quantizer:
 
     _ENTRY = {(False, False): "skml_dense_encode_f32", (False, True): "skml_dense_encode_f64",
               (True, False): "skml_dense_encode_uniform_f32", (True, True): "skml_dense_encode_uniform_f64"}
+    # the quantile quantizer's single-sketch encode reads bf16 / fp16 as they are; every other
+    # form (uniform, parallel, sharded, batch) takes the fp32 upcast, which gives the same result
+    _ENTRY_LOWP = {torch.bfloat16: "skml_dense_encode_bf16", torch.float16: "skml_dense_encode_f16"}
+    _DECODE = {torch.float32: "skml_dense_decode_f32", torch.float64: "skml_dense_decode_f64",
+               torch.bfloat16: "skml_dense_decode_bf16", torch.float16: "skml_dense_decode_f16"}
 
     def _encode(self, values, dedup: bool, uniform: bool = False, threads: int = 1):
         if self._deferred and self.payload is not None and self._hdr is None and not uniform:
@@ -103,6 +108,9 @@ class Quantizer:
                 self.payload = None  # reported once; the next quantize starts clean
                 raise
         x = as_device_values(values, self.device)
+        lowp = x.dtype in LOWP_DTYPES
+        if lowp and (uniform or threads > 1):
+            x, lowp = as_device_f32(x), False
         self._wide = x.dtype == torch.float64
         self.device = x.device
         self.n = x.numel()
@@ -122,7 +130,7 @@ class Quantizer:
             st = fn(self._ctx().handle, C.c_void_p(x.data_ptr()), self.n, threads, C.byref(p),
                     C.c_void_p(self.payload.data_ptr()), nbytes)
         else:
-            fn = getattr(_lib.lib, self._ENTRY[(uniform, self._wide)])
+            fn = getattr(_lib.lib, self._ENTRY_LOWP[x.dtype] if lowp else self._ENTRY[(uniform, self._wide)])
             st = fn(self._ctx().handle, C.c_void_p(x.data_ptr()), self.n, C.byref(p),
                     C.c_void_p(self.payload.data_ptr()), nbytes)
         check(st, "quantize")
@@ -136,6 +144,8 @@ class Quantizer:
         """Quantise shard `shard` of one logical gradient against the split table of the merged
         shard sketches (skml_dense_encode_sharded_f32); records = all shards' records in order."""
         x = as_device_values(values, self.device)
+        if x.dtype in LOWP_DTYPES:
+            x = as_device_f32(x)
         self._wide = x.dtype == torch.float64
         self.device = x.device
         self.n = x.numel()
@@ -237,8 +247,10 @@ class Quantizer:
         self._hdr = None
 
     def decode(self, out: torch.Tensor = None, dtype=None) -> torch.Tensor:
-        """values[bins[i]] on the device (DenseVectorCompressor.decompressDense): fp32 for fp32
-        input, fp64 (the reference's double[]) for fp64 input or dtype=torch.float64."""
+        """values[bins[i]] on the device (DenseVectorCompressor.decompressDense): fp32 by default
+        (also for bf16 / fp16 input), fp64 (the reference's double[]) for fp64 input or
+        dtype=torch.float64; dtype=torch.bfloat16 / torch.float16 (or such an `out`) gives the fp32
+        value rounded to nearest even, with no fp32 intermediate."""
         self._load_header()
         if dtype is None:
             dtype = out.dtype if out is not None else (torch.float64 if self._wide else torch.float32)
@@ -246,7 +258,9 @@ class Quantizer:
             out = torch.empty(self.n, dtype=dtype, device=self.device)
         if out.dtype != dtype or out.numel() != self.n or not out.is_contiguous():
             raise SketchMLException("decode: output must be a contiguous tensor of n values of the decode dtype")
-        fn = _lib.lib.skml_dense_decode_f64 if dtype == torch.float64 else _lib.lib.skml_dense_decode_f32
+        if dtype not in self._DECODE:
+            raise SketchMLException(f"decode: unsupported dtype {dtype}")
+        fn = getattr(_lib.lib, self._DECODE[dtype])
         check(fn(self._ctx().handle, C.c_void_p(self.payload.data_ptr()), C.c_void_p(out.data_ptr()), self.n),
               "decode")
         return out
@@ -316,6 +330,7 @@ class QuantileQuantizer(Quantizer):
         skml_dense_encode_batch_f32, which overlaps one bucket's sketch with the previous
         bucket's quantize pass on two streams."""
         xs = [as_device_values(b) for b in buckets]
+        xs = [as_device_f32(x) if x.dtype in LOWP_DTYPES else x for x in xs]  # the batch entry is fp32
         qs = [cls(binNum, seed) for _ in xs]
         if not xs:
             return qs

@@ -160,6 +160,14 @@ __device__ __forceinline__ uint32_t wave_reduce_u32_lane63(uint32_t v) {
     return (uint32_t)x;
 }
 
+// The same reductions with the result in every lane (wave-uniform, a scalar register).
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_reduce_u32_lane63<0>(v), 63);
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_reduce_u32_lane63<1>(v), 63);
+}
+
 // Sort elements are uint32 total-order keys, raw floats or raw doubles.  Floats and doubles
 // compare with v_min/v_max(/v_med3)_f32/f64, which on gfx950 order -0.0 before 0.0 like
 // Arrays.sort (tools/ubench/zero_minmax.hip) and drop NaN, so the leaf flags NaN from a class
@@ -184,6 +192,18 @@ __device__ __forceinline__ float sel_of<float>(bool upper) {
 template <>
 __device__ __forceinline__ double sel_of<double>(bool upper) {
     return __longlong_as_double(upper ? 0x7FF0000000000000LL : (long long)0xFFF0000000000000ULL);
+}
+// The float selector straight from bit (31 - shl) of `word`: set -> +inf, clear -> -inf.  The two
+// infinities differ in the sign bit alone, so this is a shift and an and-xor (one v_bitop3_b32)
+// where sel_of(bool) costs a v_cmp and a v_cndmask after the bit test.
+__device__ __forceinline__ float sel_of_bit(uint32_t word, uint32_t shl) {
+    return __uint_as_float(((word << shl) & 0x80000000u) ^ 0xFF800000u);
+}
+// Selector of a lane for the exchange across lane bit D (a power of two): upper when the bit is set.
+template <typename T, int D>
+__device__ __forceinline__ T sel_of_lane(int lane) {
+    if constexpr (std::is_same<T, float>::value) return sel_of_bit((uint32_t)lane, 31 - __builtin_ctz(D));
+    else return sel_of<T>((lane & D) != 0);
 }
 
 // How each element type is held in LDS / global node buffers (float for keys and floats,
@@ -373,7 +393,8 @@ __device__ __forceinline__ double med3(double a, double b, double c) {
 // Flip stage across a block of (M+1) lanes: element (lane, r) meets (lane^M, R-1-r).
 template <int R, int M, typename T>
 __device__ __forceinline__ void flip_lanes(T (&v)[R], int lane) {
-    const T sel = sel_of<T>((lane & ((M + 1) >> 1)) != 0);
+    constexpr int kBit = (M + 1) / 2;  // the top lane bit of the block
+    const T sel = sel_of_lane<T, kBit>(lane);
 #pragma unroll
     for (int r = 0; r < R / 2; r++) {
         const T pa = lane_xor<M>(v[R - 1 - r]);
@@ -387,7 +408,7 @@ __device__ __forceinline__ void flip_lanes(T (&v)[R], int lane) {
 
 template <int R, int D, typename T>
 __device__ __forceinline__ void halfclean_lanes(T (&v)[R], int lane) {
-    const T sel = sel_of<T>((lane & D) != 0);
+    const T sel = sel_of_lane<T, D>(lane);
 #pragma unroll
     for (int r = 0; r < R; r++) {
         v[r] = med3(v[r], lane_xor<D>(v[r]), sel);
@@ -444,8 +465,9 @@ __device__ __forceinline__ void compact_regs(const uint32_t (&v)[R], uint32_t (&
 // The last in-register stage of a bitonic merge compares positions (2j, 2j+1) and the
 // compaction that follows keeps one of them: fused into one v_med3 per pair, selecting
 // min (even position kept) or max (odd position kept).
+// (_sel: the caller already holds the selector, sel_of(odd) or sel_of_bit of the draw word)
 template <int R, typename T>
-__device__ __forceinline__ void halfclean_regs_compact(T (&v)[R], T (&w)[R / 2], bool odd) {
+__device__ __forceinline__ void halfclean_regs_compact_sel(T (&v)[R], T (&w)[R / 2], T sel) {
 #pragma unroll
     for (int d = R >> 1; d >= 2; d >>= 1) {
 #pragma unroll
@@ -454,18 +476,25 @@ __device__ __forceinline__ void halfclean_regs_compact(T (&v)[R], T (&w)[R / 2],
             if (j > i) ce(v[i], v[j]);
         }
     }
-    const T sel = sel_of<T>(odd);
 #pragma unroll
     for (int j = 0; j < R / 2; j++) w[j] = med3(v[2 * j], v[2 * j + 1], sel);
+}
+template <int R, typename T>
+__device__ __forceinline__ void halfclean_regs_compact(T (&v)[R], T (&w)[R / 2], bool odd) {
+    halfclean_regs_compact_sel<R>(v, w, sel_of<T>(odd));
 }
 
 // merge_group + compaction
 template <int R, typename T>
-__device__ __forceinline__ void merge_group_compact(T (&v)[R], T (&w)[R / 2], int lane, bool odd) {
+__device__ __forceinline__ void merge_group_compact_sel(T (&v)[R], T (&w)[R / 2], int lane, T sel) {
     constexpr int G = 256 / R;
     flip_lanes<R, G - 1>(v, lane);
     halfclean_lanes_down<R, G / 4>(v, lane);
-    halfclean_regs_compact<R>(v, w, odd);
+    halfclean_regs_compact_sel<R>(v, w, sel);
+}
+template <int R, typename T>
+__device__ __forceinline__ void merge_group_compact(T (&v)[R], T (&w)[R / 2], int lane, bool odd) {
+    merge_group_compact_sel<R>(v, w, lane, sel_of<T>(odd));
 }
 
 // sort_group256 + compaction (the last merge's final stage fused with the selection)
@@ -502,6 +531,38 @@ __device__ __forceinline__ uint64_t lcg_jump(const uint64_t* __restrict__ tab, u
         }
     }
     return s;
+}
+// The same jump for a wave-uniform `steps` (and s): the table is read through the constant address
+// space, so the loads are scalar loads and the multiplies run on the scalar unit.  The table is
+// written once, when the context is made, and never while a kernel runs.
+__device__ __forceinline__ uint64_t lcg_jump_uniform(const uint64_t* __restrict__ tab, uint64_t s, uint64_t steps) {
+    typedef const uint64_t __attribute__((address_space(4))) * ctab_t;
+    const ctab_t t = (ctab_t)(uintptr_t)tab;
+    const uint32_t st = __builtin_amdgcn_readfirstlane((uint32_t)steps);  // steps < 2^32 (4 table levels)
+    uint64_t a[4], c[4];  // all four loads in flight before the first multiply
+#pragma unroll
+    for (int lvl = 0; lvl < 4; lvl++) {
+        const uint32_t b = (st >> (8 * lvl)) & 255u;  // entry 0 of a level is the identity (1, 0)
+        a[lvl] = t[(lvl * 256 + b) * 2];
+        c[lvl] = t[(lvl * 256 + b) * 2 + 1];
+    }
+#pragma unroll
+    for (int lvl = 0; lvl < 4; lvl++) s = (a[lvl] * s + c[lvl]) & kLcgMask;
+    return s;
+}
+// next(1), i.e. bit 47, of the state a * s + c (mod 2^48), for a per-lane (a, c) and s < 2^48.
+// Bits 32..47 of the sum are the low 16 bits of hi32(a_lo * s_lo + c) + a_lo * s_hi + a_hi * s_lo,
+// and the low 16 bits of those two products depend on their operands' low 16 bits only: one
+// v_mad_u64_u32 and two full-rate 24-bit multiply-adds instead of a 64-bit product (three
+// quarter-rate multiplies).  (Inline asm: with bit 15 alone demanded the compiler drops the 24-bit
+// form of __umul24 and selects v_mul_lo_u32.)
+__device__ __forceinline__ uint32_t lcg_step_next1(uint64_t a, uint64_t c, uint64_t s) {
+    const uint32_t alo = (uint32_t)a, ahi = (uint32_t)(a >> 32), slo = (uint32_t)s, shi = (uint32_t)(s >> 32);
+    const uint64_t p = (uint64_t)alo * slo + c;
+    uint32_t hi = (uint32_t)(p >> 32);
+    asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(hi) : "v"(alo), "v"(shi));
+    asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(hi) : "v"(ahi), "v"(slo));
+    return (hi >> 15) & 1u;
 }
 // next(1) of the idx-th draw (0-based) from Random(seed) whose scrambled state is s0.
 __device__ __forceinline__ uint32_t lcg_bit(const uint64_t* __restrict__ tab, uint64_t s0,

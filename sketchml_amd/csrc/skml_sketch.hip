@@ -435,9 +435,9 @@ __device__ __forceinline__ void leaf2_wave(const X* __restrict__ x, int64_t chun
         const uint64_t start = node_bit_index((uint64_t)c0, 0);
         uint64_t mask;
         {
-            const uint64_t s_start = lcg_jump(tab, s0, start + 1);
-            const uint64_t s = lane == 0 ? s_start : ((ta * s_start + tc) & kLcgMask);
-            mask = __ballot((s >> 47) & 1ull);
+            // `tile` is wave-uniform (the callers pass a scalar), so the jump is scalar work
+            const uint64_t s_start = lcg_jump_uniform(tab, s0, start + 1);
+            mask = __ballot(lcg_step_next1(ta, tc, s_start));  // lane 0's (A^0, C_0) is the identity
         }
         if constexpr (STAGE == 0) {
 #pragma unroll
@@ -529,15 +529,19 @@ __device__ __forceinline__ void leaf2_wave(const X* __restrict__ x, int64_t chun
         // a level-6 tree (bit 6 of the chunk count) is this single node
         if (((chunks >> 6) & 1) && tile == ((chunks >> 7) << 1)) store_node<2>(top, lane, roots + (size_t)6 * kK);
     }
-    // per-wave partial: min / max / flags (NaN keys lie outside [key(-inf), key(+inf)])
+    // per-wave partial: min / max / flags (NaN keys lie outside [key(-inf), key(+inf)]); the flags
+    // come from ballots, so every lane holds the wave's already
+    if constexpr (std::is_same<Key, uint32_t>::value) {
+        mn = wave_min_u32(mn);
+        mx = wave_max_u32(mx);
+    } else {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const Key omn = __shfl_xor(mn, off, 64);
-        const Key omx = __shfl_xor(mx, off, 64);
-        const uint32_t ofl = (uint32_t)__shfl_xor((int)fl, off, 64);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-        fl |= ofl;
+        for (int off = 32; off >= 1; off >>= 1) {
+            const Key omn = __shfl_xor(mn, off, 64);
+            const Key omx = __shfl_xor(mx, off, 64);
+            mn = omn < mn ? omn : mn;
+            mx = omx > mx ? omx : mx;
+        }
     }
     if (lane == 0) {
         typename LeafTypes<E>::Part p;
@@ -564,7 +568,7 @@ __global__ __launch_bounds__(256, LeafTypes<E>::kMinWaves) void k_leaf2(
     typename LeafTypes<E>::Part* __restrict__ part, E* __restrict__ nodes6, E* __restrict__ roots, int64_t tile0,
     uint8_t* __restrict__ ubits = nullptr) {
     __shared__ E fb[kLeaf2Waves][kWaveFb];
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     leaf2_wave<STAGE, PARTIAL, E, X>(x, chunks, s0, tab, part, nodes6, roots,
                                   tile0 + (int64_t)blockIdx.x * kLeaf2Waves + wave, ubits, fb[wave]);
 }
@@ -608,7 +612,9 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
     auto& fb = L.fb;
     auto& stk = L.stk;
     auto& wpart = L.wpart;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the wave index through readfirstlane: the compiler then knows that c0, the round's first draw
+    // and the whole jump to it are wave-uniform and keeps them on the scalar unit
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int64_t c_tile = tile * kLeafWaveChunks;
     if (c_tile >= chunks) return;  // workgroup-uniform under SPLIT, wave-uniform otherwise
 #ifdef SKML_PROF_LEAF
@@ -703,11 +709,13 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
             const uint64_t start = node_bit_index((uint64_t)c0, 0);
             uint64_t mask;
             {
-                // A^ln, C_lane reloaded each round (L2-resident) rather than held in 4 registers
-                const uint64_t ta = tab[ln * 2], tc = tab[ln * 2 + 1];
-                const uint64_t s_start = lcg_jump(tab, s0, start + 1);
-                const uint64_t s = ln == 0 ? s_start : ((ta * s_start + tc) & kLcgMask);
-                mask = __ballot((s >> 47) & 1ull);
+                // A^ln, C_lane reloaded each round (L2-resident) rather than held in 4 registers;
+                // lane 0's entry is the identity.  The jump to `start` is scalar work, the one
+                // per-lane step keeps only the bits that decide next(1).
+                const ulonglong2 t = reinterpret_cast<const ulonglong2*>(tab)[(uint32_t)ln];
+                const uint64_t ta = t.x, tc = t.y;
+                const uint64_t s_start = lcg_jump_uniform(tab, s0, start + 1);
+                mask = __ballot(lcg_step_next1(ta, tc, s_start));
             }
             neg_any = neg_any || (rfl & 2u);
             pos_any = pos_any || (rfl & 4u);
@@ -720,6 +728,12 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
             auto bit = [&](int level, int d) -> uint32_t {
                 return (uint32_t)(mask >> (2 * d - __popc((unsigned)d) + level)) & 1u;
             };
+            // The fast path takes the compaction selector straight from the draw word: levels 0..4
+            // use offsets <= 30, so the low word does, shifted so that the draw lands on the sign bit.
+            const uint32_t mask_lo = (uint32_t)mask;
+            auto dsel = [&](int level, int d) -> float {
+                return sel_of_bit(mask_lo, (uint32_t)(31 - level - 2 * d + __popc((unsigned)d)));
+            };
             float w1[32];
             sort_regs_oddeven<64>(v);
             sort_lanes_upto128<64, 128>(v, ln);  // two sorted 128-runs per chunk
@@ -728,7 +742,8 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
                 mn = k0 < mn ? k0 : mn;
                 mx = k63 > mx ? k63 : mx;
             }
-            merge_group_compact<64>(v, w1, ln, bit(0, ln >> 2) != 0);
+            if constexpr (!EX) merge_group_compact_sel<64>(v, w1, ln, dsel(0, ln >> 2));
+            else merge_group_compact<64>(v, w1, ln, bit(0, ln >> 2) != 0);
             // levels 1..4 in registers: 8, 16, 32, 64 lanes per merge
             float w2[16], w3[8], w4[4], n4[2];
 #ifdef SKML_LEAF_ABLATE_TREE  // profiling ablation: levels 1..4 replaced by a fold (wrong results)
@@ -738,10 +753,17 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
             n4[0] = w4[0];
             n4[1] = w4[2];
 #else
-            wave_level<32>(w1, w2, ln, bit(1, 2 * (ln >> 3) + 1), exact, wfb);
-            wave_level<16>(w2, w3, ln, bit(2, 4 * (ln >> 4) + 3), exact, wfb);
-            wave_level<8>(w3, w4, ln, bit(3, 8 * (ln >> 5) + 7), exact, wfb);
-            wave_level<4>(w4, n4, ln, bit(4, 15), exact, wfb);
+            if constexpr (!EX) {
+                merge_group_compact_sel<32>(w1, w2, ln, dsel(1, 2 * (ln >> 3) + 1));
+                merge_group_compact_sel<16>(w2, w3, ln, dsel(2, 4 * (ln >> 4) + 3));
+                merge_group_compact_sel<8>(w3, w4, ln, dsel(3, 8 * (ln >> 5) + 7));
+                merge_group_compact_sel<4>(w4, n4, ln, dsel(4, 15));
+            } else {
+                wave_level<32>(w1, w2, ln, bit(1, 2 * (ln >> 3) + 1), exact, wfb);
+                wave_level<16>(w2, w3, ln, bit(2, 4 * (ln >> 4) + 3), exact, wfb);
+                wave_level<8>(w3, w4, ln, bit(3, 8 * (ln >> 5) + 7), exact, wfb);
+                wave_level<4>(w4, n4, ln, bit(4, 15), exact, wfb);
+            }
 #endif
             if constexpr (SPLIT) {  // the cross-wave levels follow the round loops
                 stk[wave][0][ln] = make_float2(n4[0], n4[1]);
@@ -771,15 +793,9 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
     if constexpr (SPLIT) {
         if (!run_round(std::false_type{}, wave)) run_round(std::true_type{}, wave);
         // per-wave partial, then levels 5 and 6 across the waves
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const uint32_t omn = __shfl_xor(mn, off, 64);
-            const uint32_t omx = __shfl_xor(mx, off, 64);
-            const uint32_t ofl = (uint32_t)__shfl_xor((int)fl, off, 64);
-            mn = omn < mn ? omn : mn;
-            mx = omx > mx ? omx : mx;
-            fl |= ofl;
-        }
+        // (fl is built from ballots: every lane already holds the wave's flags)
+        mn = wave_min_u32(mn);
+        mx = wave_max_u32(mx);
         if (lane == 0) {
             wpart[wave][0] = mn;
             wpart[wave][1] = mx;
@@ -828,15 +844,8 @@ __device__ __forceinline__ void leaf64_tile(const X* __restrict__ x, int64_t chu
     store_node<2>(top, lane, nodes6 + (size_t)tile * kK);
     if (((chunks >> 6) & 1) && tile == ((chunks >> 7) << 1)) store_node<2>(top, lane, roots + (size_t)6 * kK);
     if constexpr (!SPLIT) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const uint32_t omn = __shfl_xor(mn, off, 64);
-            const uint32_t omx = __shfl_xor(mx, off, 64);
-            const uint32_t ofl = (uint32_t)__shfl_xor((int)fl, off, 64);
-            mn = omn < mn ? omn : mn;
-            mx = omx > mx ? omx : mx;
-            fl |= ofl;
-        }
+        mn = wave_min_u32(mn);
+        mx = wave_max_u32(mx);
     }
     if (lane == 0) {
         LeafPartial p;
@@ -868,7 +877,7 @@ __global__ __launch_bounds__(256, SKML_LEAF64_WAVES) void k_leaf64(const X* __re
                                                    uint8_t* __restrict__ ubits, int64_t total_chunks,
                                                    int64_t split_from) {
     __shared__ Leaf64Shared L;
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // tile indices stay scalar
     int64_t blk = blockIdx.x;
     if (total_chunks > chunks) {
         if (blk == 0) {
@@ -1260,8 +1269,11 @@ __device__ __forceinline__ float load_widen_any(const void* x, int xtype, int64_
 // load them here.
 // has_pre: `pre` holds this thread's share of the leaf partials, loaded ahead by the caller (by
 // value: a pointer to the caller's local put it in scratch memory, a store and a reload away).
+// has_rank: pre_rank is a.ranks[threadIdx.x], loaded ahead the same way (the caller checks that
+// one thread per split covers getQuantiles' loop: req_bins - 1 <= blockDim.x).
 __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_pre = false,
-                              LeafPartial pre = LeafPartial{0xFFFFFFFFu, 0u, 0u, 0u}) {
+                              LeafPartial pre = LeafPartial{0xFFFFFFFFu, 0u, 0u, 0u}, bool has_rank = false,
+                              int64_t pre_rank = 0) {
     const int t = threadIdx.x, T = blockDim.x;
     skml_dense_header* hdr = reinterpret_cast<skml_dense_header*>(a.payload);
     double* splits = reinterpret_cast<double*>(a.payload + kHeaderBytes);
@@ -1443,7 +1455,7 @@ __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_p
         if (ns == 0) {
             sp = __longlong_as_double(0x7FF8000000000000LL);  // NaN (HeapQuantileSketch.java:299-301)
         } else {
-            const int64_t rank = a.ranks[i];
+            const int64_t rank = has_rank ? pre_rank : a.ranks[i];
             int lo = 0, hi = ns;
             while (lo + 1 < hi) {
                 const int mid = (lo + hi) >> 1;
@@ -1586,6 +1598,50 @@ __device__ __forceinline__ void merge_group_wg(const MergePass& pass, int wg, co
     const int64_t node0 = job.src_node + ((int64_t)grp << g);
     const int64_t chunk0 = job.chunk_base + ((int64_t)grp << (g + L));
     E* out = job.root_level >= 0 ? roots + (size_t)job.root_level * kK : dst + (size_t)(job.dst_node + grp) * kK;
+    // A group of 4 nodes (the last pass of a 2^28 bucket): two levels in wave 0 alone, 16 lanes per
+    // node and 8 keys per lane (two pair merges, then one), where the 64-node machinery below runs
+    // three in-wave levels of 16 keys per lane in all 8 waves and a barrier.  The first pass keeps
+    // the general form: it also reduces the leaf partials.
+    if constexpr (!std::is_same<E, double>::value) {
+        if (g == 2 && !(part_red && L == kLeafTopLevel)) {
+            if (wave != 0) return;
+            // compaction bits: lanes 0, 1 the pair merges (last nodes 1, 3), lane 2 the final one
+            uint32_t bsel = 0;
+            if (lane < 3) {
+                const int lo = lane < 2 ? 1 : 2, last_node = lane < 2 ? 2 * lane + 1 : 3;
+                const int lvl = L + lo;
+                const int64_t i = ((chunk0 + ((int64_t)(last_node + 1) << L)) >> lvl) - 1;
+                const int64_t cnt = upper_node_count(uchunks);
+                int64_t idx = upper_level_offset(uchunks, lvl) + i;
+                idx = idx < cnt ? idx : cnt - 1;
+                bsel = ubits[idx < 0 ? 0 : idx];
+            }
+            const float4* p = reinterpret_cast<const float4*>(src + (size_t)(node0 + (lane >> 4)) * kK) + (lane & 15) * 2;
+            T w1[8], w2[4], w3[2];
+            uint32_t fl = 0;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const float4 f = p[q];
+                const uint32_t b[4] = {__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z),
+                                       __float_as_uint(f.w)};
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    fl |= (b[e] == 0x80000000u) ? 2u : 0u;
+                    fl |= (b[e] == 0u) ? 4u : 0u;
+                    w1[q * 4 + e] = f2key(b[e]);
+                }
+            }
+            SKML_PROF_AT(1);
+            const uint32_t bits = (uint32_t)__ballot(bsel != 0);
+            const bool wexact = (__ballot((fl & 2u) != 0) != 0) && (__ballot((fl & 4u) != 0) != 0);
+            wave_level<8>(w1, w2, lane, (bits >> (lane >> 5)) & 1u, wexact, sh.fb[0]);
+            wave_level<4>(w2, w3, lane, (bits >> 2) & 1u, wexact, sh.fb[0]);
+            SKML_PROF_AT(2);
+            store_node<2>(w3, lane, out);
+            SKML_PROF_AT(3);
+            return;
+        }
+    }
     if (tid == 0) sh.flags = 0u;
     // this lane's compaction bit, drawn by the leaf (k_leaf2, upper_level_offset numbering); the
     // load is issued first so its latency hides behind the node loads.  Padding merges (g < 6)
@@ -1735,6 +1791,11 @@ __global__ __launch_bounds__(512) void k_merge(MergePass pass, MergePass next, c
     const int64_t npre = sa.nred + (sa.nparts - sa.part_from);
     const bool prefetch = pass.fuse_summary || next.fuse_summary ? npre <= (int64_t)blockDim.x : false;
     if (prefetch && tid < npre) pre = tid < sa.nred ? sa.part_red[tid] : sa.part[sa.part_from + (tid - sa.nred)];
+    // and getQuantiles' ranks (fixed per n and bins, written before this encode): one per thread
+    const int nsplit = sa.req_bins - 1;
+    const bool rank_ahead = (pass.fuse_summary || next.fuse_summary) && nsplit <= (int)blockDim.x;
+    int64_t pre_rank = 0;
+    if (rank_ahead && tid < nsplit) pre_rank = sa.ranks[tid];
     if (has_next) {
         SKML_PROF(0);
         // the trailing pass's merges (independent trees), one after another in this workgroup
@@ -1750,7 +1811,7 @@ __global__ __launch_bounds__(512) void k_merge(MergePass pass, MergePass next, c
         if (!next.fuse_summary) return;
     }
     SKML_PROF(1);
-    summary_block(sa, U.s, prefetch, pre);
+    summary_block(sa, U.s, prefetch, pre, rank_ahead, pre_rank);
 #ifdef SKML_PROF_WARM
     // diagnostic build: the summary again with warm instruction / data caches (phases 2..10 then
     // hold the second run; 26 / 27 bracket it)

@@ -379,9 +379,20 @@ int skml_ctx_create(int device, void* hip_stream, skml_ctx** out) {
     }
     std::vector<uint64_t> tab;
     build_jump_table(tab);
-    hipError_t e = hipMalloc(&c->jump_tab, tab.size() * sizeof(uint64_t));
-    if (e == hipSuccess)
-        e = hipMemcpy(c->jump_tab, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    // Uploaded on the context's own stream from its pinned staging buffer, complete before the
+    // context exists.  A hipMemcpy goes through the null stream, and an async copy out of pageable
+    // memory waits for it too while the runtime registers the host pages: either way the creation
+    // (and the first batched encode, which creates the side context) stalled behind whatever the
+    // null stream was running.
+    const size_t tab_bytes = tab.size() * sizeof(uint64_t);
+    hipError_t e = hipMalloc(&c->jump_tab, tab_bytes);
+    void* pin = e == hipSuccess ? skml::ctx_pinned(c, tab_bytes) : nullptr;
+    if (e == hipSuccess && !pin) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) {
+        std::memcpy(pin, tab.data(), tab_bytes);
+        e = hipMemcpyAsync(c->jump_tab, pin, tab_bytes, hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         skml_ctx_destroy(c);
         return fail(SKML_E_HIP, "jump table: %s", hipGetErrorString(e));
@@ -1224,9 +1235,13 @@ static int dense_decode_sum_x(skml_ctx* c, const void* payloads, int32_t P, size
     HIP_TRY(hipSetDevice(c->device));
     // Gradient.sum adds gradients of one dimension (ml/gradient/Gradient.scala:44-49): every
     // payload must be a finished dense payload of exactly n codes that fits its stride.
-    skml_dense_header h[16];
-    HIP_TRY(hipMemcpy2DAsync(h, sizeof(skml_dense_header), payloads, stride, sizeof(skml_dense_header), (size_t)P,
-                             hipMemcpyDeviceToHost, c->stream));
+    // the headers come back through the context's pinned staging, one copy each: a 2D copy into
+    // pageable memory waits for the null stream, whatever stream it is given
+    skml_dense_header* h = static_cast<skml_dense_header*>(skml::ctx_pinned(c, sizeof(skml_dense_header) * 16));
+    if (!h) return fail(SKML_E_OOM, "pinned staging of the payload headers");
+    for (int p = 0; p < P; p++)
+        HIP_TRY(hipMemcpyAsync(h + p, static_cast<const char*>(payloads) + (size_t)p * stride, sizeof(skml_dense_header),
+                               hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int p = 0; p < P; p++) {
         if (h[p].magic != SKML_DENSE_MAGIC) return fail(SKML_E_STATE, "payload %d is not a dense payload", p);
@@ -1394,9 +1409,10 @@ int skml_dense_deserialize_ref(skml_ctx* c, const uint8_t* buf, size_t len, void
     HIP_TRY(hipMemcpyAsync(&nbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (nbad) {
-        // leave no usable payload behind
+        // leave no usable payload behind (on the context's stream, never the null stream)
         const uint32_t zero = 0;
-        HIP_TRY(hipMemcpy(payload, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpyAsync(payload, &zero, sizeof(zero), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         return fail(SKML_E_ARG, "bin outside [0, %d) in the stream", B);
     }
     return SKML_OK;

@@ -1964,6 +1964,9 @@ int skml_sparse_export(skml_ctx* c, const skml_sparse* s, void* dst, size_t cap)
     if (s->n_delta_words > 0)
         SP_HIP(hipMemcpyAsync(d + L.off_deltas, s->delta_words, sizeof(uint64_t) * (size_t)s->n_delta_words,
                               hipMemcpyDeviceToDevice, st));
+    // the copies read the payload's block: they complete before the call returns, so a payload
+    // freed right after its export hands the pool a block with no pending reader (BlockPool)
+    SP_HIP(hipStreamSynchronize(st));
     return SKML_OK;
 }
 

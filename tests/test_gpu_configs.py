@@ -197,7 +197,8 @@ def test_batch_encode_fresh_side_lane_on_recycled_memory(gpu):
     the new workspaces are likely to reuse it; every batched payload must carry a finished header
     and equal the same bucket encoded alone on the shared context, byte for byte.  The race is
     timing-dependent: a build with the null-stream zeroing also passed this test on one box
-    (DESIGN.md §0); it failed 3 of 5 full-suite runs through the C4 test above."""
+    (DESIGN.md §0); it failed 3 of 5 full-suite runs through the C4 test above.
+    The deterministic guard is tests/test_gpu_stream_order.py::test_dense_encode_batch (pattern B)."""
     from sketchml_amd.context import Context
     L = _lib()
     P, n = 4, 2**20 + 512

@@ -277,6 +277,73 @@ int skml_dense_serialize_ref(skml_ctx* ctx, const void* payload_dev, uint8_t* bu
 int skml_dense_deserialize_ref(skml_ctx* ctx, const uint8_t* buf_host, size_t len,
                                void* payload_dev, size_t payload_cap);
 
+/* ---- FixedPointGradient (ml/gradient/FixedPointGradient.scala:39-75): the norm-scaled
+ * sign + (b-1)-bit magnitude baseline codec that Gradient.compress switches to beside the sketch
+ * (ml/gradient/Gradient.scala:18-36) ---- */
+
+#define SKML_FIXED_MAGIC 0x584D4B53u /* "SKMX" */
+
+/* Device payload: this header (little-endian, 64 bytes) padded with zeros to 256 bytes, then
+ * ceil(n * num_bits / 64) 64-bit words, padded with zero words to a multiple of 256 bytes.  Code i
+ * occupies stream bits [i * num_bits, (i + 1) * num_bits), its most significant bit first
+ * (BinaryUtils.setBits, sketch/binary/BinaryUtils.java:6-14); stream bit k is bit k & 63 of word
+ * k >> 6 (java.util.BitSet.toLongArray).  Caller-owned and relocatable: skml_allgather moves it
+ * as it is. */
+typedef struct skml_fixed_header {
+    uint32_t magic;
+    int32_t status;   /* SKML_OK, or SKML_E_NAN: a NaN or infinite value, a norm that is not finite,
+                         or a zero norm over a nonzero value (fp64 underflow) */
+    int64_t n;        /* FixedPointGradient.size */
+    int32_t num_bits; /* 2..29 */
+    int32_t reserved0;
+    double norm;      /* sqrt(sum v_i^2) times every timesBy factor */
+    int64_t words_offset; /* 256 */
+    int64_t seed;     /* the sigma stream: sigma_i = the i-th nextBoolean() of java.util.Random(seed) */
+    int64_t reserved[2];
+} skml_fixed_header;
+
+/* Bytes of a device payload for n codes of num_bits; 0 for arguments the encode refuses. */
+size_t skml_fixed_payload_bytes(int64_t n, int32_t num_bits);
+
+/* FixedPointGradient.fromArray (FixedPointGradient.scala:39-53): norm = sqrt(sum v_i^2) in double;
+ * code_i = floor(|v_i| / norm * (2^(b-1) - 1)).toInt + sigma_i, or-ed with 2^(b-1) when v_i < 0,
+ * all in double in that order (fp32 input is widened first).  sigma_i is added unconditionally, so
+ * |v_i| = norm with sigma_i = 1 gives the code 2^(b-1), which decodes as -0.0; an all-zero input
+ * (norm 0, NaN quotient, .toInt = 0) gives code_i = sigma_i.  The reference draws sigma from an
+ * unseeded global Bernoulli(0.5); here it is the i-th nextBoolean() of java.util.Random(seed),
+ * i from 0.  The sum of squares is a fixed tree (no atomics): the same input gives the same bytes
+ * on every run, and its relative error is below 2^-40.  num_bits outside 2..29 (the reference
+ * requires < 30; 1 divides by zero) and n outside 1..2^31-1 return SKML_E_ARG.  x_dev 16-byte
+ * aligned, payload_dev 256-byte aligned.  Asynchronous; the header's status reports the input.
+ * Timed (skml_ctx_set_timing) as SKML_K_SUMMARY for the norm and header launches and
+ * SKML_K_QUANTIZE for the quantize + pack pass; the decodes as SKML_K_DECODE / SKML_K_DECODE_SUM. */
+int skml_fixed_encode_f32(skml_ctx* ctx, const float* x_dev, int64_t n, int32_t num_bits, int64_t seed,
+                          void* payload_dev, size_t payload_cap);
+int skml_fixed_encode_f64(skml_ctx* ctx, const double* x_dev, int64_t n, int32_t num_bits, int64_t seed,
+                          void* payload_dev, size_t payload_cap);
+
+/* FixedPointGradient.toArray (FixedPointGradient.scala:63-75): v_i = (double)(code_i & max) / max *
+ * norm, negated when the sign bit is set; the f32 form stores (float)v_i.  out_dev 16-byte
+ * aligned.  Asynchronous. */
+int skml_fixed_decode_f32(skml_ctx* ctx, const void* payload_dev, float* out_dev, int64_t n);
+int skml_fixed_decode_f64(skml_ctx* ctx, const void* payload_dev, double* out_dev, int64_t n);
+
+/* Gradient.sum + timesBy over P fixed-point payloads `stride` bytes apart, skml_dense_decode_sum_f32's
+ * contract: out[i] = (float)(scale * sum_p v_p[i]), the sum in double from +0.0 in payload order.
+ * Every payload must hold n codes of one num_bits (else SKML_E_ARG) and fit its stride; P in
+ * [1, 16].  Reads the headers back first (synchronises), then queues the sum. */
+int skml_fixed_decode_sum_f32(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride,
+                              float* out_dev, int64_t n, double scale);
+
+/* The codes as int32 (BinaryUtils.getBits of every field).  Asynchronous. */
+int skml_fixed_codes_i32(skml_ctx* ctx, const void* payload_dev, int32_t* codes_dev, int64_t n);
+
+/* FixedPointGradient.timesBy (FixedPointGradient.scala:55): norm *= x, nothing else.  Asynchronous. */
+int skml_fixed_times_by(skml_ctx* ctx, void* payload_dev, double x);
+
+/* Synchronise and read the header; returns its status (SKML_E_NAN as described above). */
+int skml_fixed_info(skml_ctx* ctx, const void* payload_dev, skml_fixed_header* hdr_host);
+
 /* ---- Host memory in and out (the JNI path: a JVM float[] on its way to a socket) ---- */
 
 /* Pinned host memory (hipHostMalloc): a Java direct ByteBuffer over it (JNI NewDirectByteBuffer)

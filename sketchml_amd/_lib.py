@@ -29,6 +29,7 @@ SKML_E_OOM = 6
 SKML_E_STATE = 7
 UNIQUE_ID_BYTES = 128
 SKML_MAX_BINS = 65536
+SKML_FIXED_MAGIC = 0x584D4B53
 SKML_QUANTILE = 0
 SKML_UNIFORM = 1
 
@@ -64,6 +65,13 @@ class DenseHeader(C.Structure):
                 ("bin_num", C.c_int32), ("zero_idx", C.c_int32), ("code_bits", C.c_int32),
                 ("req_bins", C.c_int32), ("min", C.c_double), ("max", C.c_double),
                 ("codes_offset", C.c_int64), ("reserved", C.c_int64)]
+
+
+class FixedHeader(C.Structure):
+    """skml_fixed_header (include/skml.h): the 64-byte header of a FixedPointGradient payload."""
+    _fields_ = [("magic", C.c_uint32), ("status", C.c_int32), ("n", C.c_int64), ("num_bits", C.c_int32),
+                ("reserved0", C.c_int32), ("norm", C.c_double), ("words_offset", C.c_int64), ("seed", C.c_int64),
+                ("reserved", C.c_int64 * 2)]
 
 
 class SparseGroup(C.Structure):
@@ -121,6 +129,15 @@ _SIGS = {
     "skml_dense_times_by": (C.c_int, [vp, vp, C.c_double]),
     "skml_dense_serialize_ref": (C.c_int, [vp, vp, u8p, C.c_size_t, szp]),
     "skml_dense_deserialize_ref": (C.c_int, [vp, u8p, C.c_size_t, vp, C.c_size_t]),
+    "skml_fixed_payload_bytes": (C.c_size_t, [i64, i32]),
+    "skml_fixed_encode_f32": (C.c_int, [vp, vp, i64, i32, i64, vp, C.c_size_t]),
+    "skml_fixed_encode_f64": (C.c_int, [vp, vp, i64, i32, i64, vp, C.c_size_t]),
+    "skml_fixed_decode_f32": (C.c_int, [vp, vp, vp, i64]),
+    "skml_fixed_decode_f64": (C.c_int, [vp, vp, vp, i64]),
+    "skml_fixed_decode_sum_f32": (C.c_int, [vp, vp, i32, C.c_size_t, vp, i64, C.c_double]),
+    "skml_fixed_codes_i32": (C.c_int, [vp, vp, vp, i64]),
+    "skml_fixed_times_by": (C.c_int, [vp, vp, C.c_double]),
+    "skml_fixed_info": (C.c_int, [vp, vp, C.POINTER(FixedHeader)]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
     "skml_host_free": (C.c_int, [vp]),
     "skml_dense_encode_host_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), vp, C.c_size_t, szp]),

@@ -188,6 +188,30 @@ hipError_t launch_decode_sum(hipStream_t st, const void* payloads, int P, size_t
 hipError_t launch_bins(hipStream_t st, const void* payload, int32_t* bins, int64_t n);
 hipError_t launch_ref_body(hipStream_t st, const void* payload, uint8_t* out, int64_t n, int width);
 hipError_t launch_times_by(hipStream_t st, void* payload, double x);
+// ---- FixedPointGradient (skml_fixed.hip) ----
+constexpr int kFxHeaderBytes = 256;   // the 64-byte header padded: the words start here
+constexpr int kFxMinBits = 2, kFxMaxBits = 29;
+constexpr int kFxMaxParts = 1024;     // workgroup partials of the sum of squares
+// One workgroup's part of the sum of squares; flags bit 0: a value that is not zero.
+struct FxPartial {
+    double sum;
+    uint32_t flags;
+    uint32_t pad;
+};
+static_assert(sizeof(skml_fixed_header) == 64, "the fixed-point header is 64 bytes");
+__host__ __device__ inline int64_t fixed_words(int64_t n, int bits) { return (n * bits + 63) >> 6; }
+// x: n values, float (wide = 0) or double; part: kFxMaxParts partials.  The norm's two launches
+// write the header (and zero its padding and the words' tail padding), the quantize pass the words.
+hipError_t launch_fixed_norm(hipStream_t st, const void* x, int wide, int64_t n, int bits, int64_t seed,
+                             FxPartial* part, void* payload);
+hipError_t launch_fixed_quantize(hipStream_t st, const void* x, int wide, int64_t n, void* payload,
+                                 const uint64_t* jump_tab);
+hipError_t launch_fixed_decode(hipStream_t st, const void* payload, void* out, int wide, int64_t n);
+// bits: the payloads' common width (checked by the caller)
+hipError_t launch_fixed_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, float* out,
+                                   int64_t n, double scale, int bits);
+hipError_t launch_fixed_codes(hipStream_t st, const void* payload, int32_t* codes, int64_t n);
+hipError_t launch_fixed_times_by(hipStream_t st, void* payload, double x);
 // ---- kernel launchers (skml_f64.hip) ----
 hipError_t launch_summary64(hipStream_t st, const double* x, int64_t n, const LeafPartial64* part, int64_t nparts,
                             const double* roots, const int64_t* ranks, int req_bins, int dedup, void* payload,

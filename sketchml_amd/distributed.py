@@ -157,6 +157,16 @@ _DECODE_SUM = {torch.float32: "skml_dense_decode_sum_f32", torch.bfloat16: "skml
                torch.float16: "skml_dense_decode_sum_f16"}
 
 
+def decode_sum_fixed_point(ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, n: int, scale: float,
+                           out: torch.Tensor) -> None:
+    """decode_sum for gathered FixedPointGradient payloads (fixed_point.encode) of one numBits and
+    n: out[i] = (float)(scale * sum_p v_p[i]), the sum in double in payload order."""
+    if out.dtype != torch.float32:
+        raise SketchMLException(f"decode_sum_fixed_point: unsupported output dtype {out.dtype}")
+    check(_lib.lib.skml_fixed_decode_sum_f32(ctx_handle, C.c_void_p(payloads.data_ptr()), nranks, stride,
+                                             C.c_void_p(out.data_ptr()), n, float(scale)), "fixed_decode_sum")
+
+
 # ---- one split table across ranks (SURVEY §8e single-split-table mode) ----------------------
 def parallel_slices(n_total: int, parts: int) -> list[int]:
     """Slice sizes of QuantileQuantizer.parallelQuantize (QuantileQuantizer.java:66-68): n/T

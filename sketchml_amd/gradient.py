@@ -14,6 +14,7 @@ from enum import Enum
 import numpy as np
 import torch
 
+from . import fixed_point
 from .exceptions import SketchMLException
 from .quantization import QuantileQuantizer
 from .sparse import encode_sparse, to_sparse
@@ -25,6 +26,7 @@ class Kind(Enum):
     DenseDouble = "DenseDouble"
     SparseDouble = "SparseDouble"
     Sketch = "Sketch"
+    FixedPoint = "FixedPoint"
 
 
 def _jint(x: int) -> int:
@@ -176,3 +178,89 @@ class SketchGradient:
 
     def kind(self) -> Kind:
         return Kind.Sketch
+
+
+class FixedPointGradient:
+    """ml/gradient/FixedPointGradient.scala:13-80, the QSGD-style baseline of Gradient.compress:
+    norm-scaled sign + (numBits - 1)-bit magnitudes with a coin flip added to every code, packed
+    into a BitSet word stream.  The payload (header with the norm, then the words) lives on the
+    device; `seed` names the coin flips (the i-th nextBoolean() of java.util.Random(seed)), which
+    the reference draws from an unseeded global Bernoulli.
+
+    fromSparse keeps the indices tensor as it is and encodes the values, as the reference does.
+    """
+
+    def __init__(self, grad=None, numBits: int = 8, seed: int = 0, dim: int | None = None):
+        if numBits >= 30 or numBits < 2:  # require(numBits < 30, ...); one bit divides by max = 0
+            raise SketchMLException(f"Bit num out of range: {numBits}")
+        self.numBits, self.seed = int(numBits), int(seed)
+        self.dim = int(dim if dim is not None else (grad.dim if grad is not None else 0))
+        self.size = 0
+        self.indices: torch.Tensor | None = None
+        self.payload: torch.Tensor | None = None
+        if grad is not None:
+            if grad.kind() == Kind.DenseDouble:
+                self.fromDense(grad)
+            elif grad.kind() == Kind.SparseDouble:
+                self.fromSparse(grad)
+            else:
+                raise SketchMLException(f"Cannot create {Kind.FixedPoint.value} from {grad.kind().value}")
+
+    def _from_array(self, values: torch.Tensor) -> None:
+        self.size = int(values.numel())
+        self.payload = fixed_point.encode(values, self.numBits, self.seed)
+
+    def fromDense(self, dense: DenseDoubleGradient) -> None:
+        self.indices = None
+        self._from_array(dense.values)
+
+    def fromSparse(self, sparse: SparseDoubleGradient) -> None:
+        self.indices = sparse.indices
+        self._from_array(sparse.values)
+
+    @property
+    def norm(self) -> float:
+        return float(fixed_point.info(self.payload).norm)
+
+    def timesBy(self, x: float) -> None:
+        fixed_point.times_by(self.payload, x)
+
+    def countNNZ(self) -> int:
+        return self.size
+
+    def _to_array(self) -> torch.Tensor:
+        return fixed_point.decode(self.payload, self.size, torch.float64)
+
+    def toDense(self) -> DenseDoubleGradient:
+        return DenseDoubleGradient(self.dim, self._to_array())
+
+    def toSparse(self) -> SparseDoubleGradient:
+        if self.indices is None:
+            raise SketchMLException("toSparse of a dense FixedPointGradient: indices is null")
+        return SparseDoubleGradient(self.dim, self.indices, self._to_array())
+
+    def toAuto(self):
+        return (self.toDense() if self.indices is None else self.toSparse()).toAuto()
+
+    def kind(self) -> Kind:
+        return Kind.FixedPoint
+
+
+def compress(grad, compressor: str = "Sketch", **conf):
+    """Gradient.compress's switch (ml/gradient/Gradient.scala:18-36) over MLConf's compressor names
+    ("Sketch", "FixedPoint", "None"; case and underscores are ignored, so "fixed_point" works).
+    conf: quantBinNum, sketchGroupNum, sketchRowNum, sketchColRatio, fixedPointBitNum (MLConf's
+    names and defaults), and seed / hashSeed for the streams this library makes explicit."""
+    name = str(compressor).replace("_", "").lower()
+    if name == "sketch":
+        return SketchGradient(grad, conf.get("quantBinNum", 256), conf.get("sketchGroupNum", 8),
+                              conf.get("sketchRowNum", 2), conf.get("sketchColRatio", 0.3),
+                              seed=conf.get("seed", 0), hashSeed=conf.get("hashSeed", 0))
+    if name == "fixedpoint":
+        return FixedPointGradient(grad, conf.get("fixedPointBitNum", 8), seed=conf.get("seed", 0))
+    if name == "none":
+        return grad
+    if name in ("zip", "float"):
+        raise SketchMLException(f"Compressor not built here: {compressor} (ZipGradient's quantizer is sequential, "
+                                f"the Float codec is a cast; DESIGN.md section 9)")
+    raise SketchMLException(f"Unrecognizable compressor: {compressor}")

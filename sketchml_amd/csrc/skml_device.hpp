@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "skml_fused_merge.hpp"
 #include "skml_internal.h"
 
 namespace skml {
@@ -314,9 +315,65 @@ __device__ __forceinline__ void sort4_3in(float& a, float& b, float& c, float& d
 #ifndef SKML_SORT4_3IN
 #define SKML_SORT4_3IN 1
 #endif
+// The merge phases after the 4-sorters in 3-input form (skml_fused_merge.hpp, generated by
+// tools/gen_fused_merge.py): a p+p merge joins two sorted runs, and those order relations let
+// min3 / med3 / max3 over a comparator's grand-operands stand for two ops, so many intermediate
+// minima and maxima are never computed (R = 64: 815 ops per lane against 1,054).  The A/B build
+// keeps the plain network.
+#ifndef SKML_FUSED_MERGE
+#ifdef SKML_AB
+#define SKML_FUSED_MERGE 0
+#else
+#define SKML_FUSED_MERGE 1
+#endif
+#endif
+
+// One op of the generated list, bare like ce(float&, float&): nothing canonicalises an operand.
+template <int K>
+__device__ __forceinline__ float fused_merge_op(float a, float b, float c) {
+    float d;
+    if constexpr (K == 0) asm("v_min_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    else if constexpr (K == 1) asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    else if constexpr (K == 2) asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    else if constexpr (K == 3) asm("v_med3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    else asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+#define SKML_FM_X(K, D, A, B, C) s[D] = fused_merge_op<K>(s[A], s[B], s[C]);
+#define SKML_FM_B() __builtin_amdgcn_sched_barrier(0);
+#define SKML_FM_O(I, S) v[I] = s[S];
+// v: sorted blocks of 4 -> sorted.  The list is straight-line code over static slot indices, so
+// every slot is a register; the barriers keep the scheduler from stretching live ranges.
+template <int R>
+__device__ __forceinline__ void fused_merge_phases(float (&v)[R]) {
+    static_assert(R == 32 || R == 64, "no generated list for this R");
+    if constexpr (R == 64) {
+        float s[SKML_FM64_SLOTS];
+#pragma unroll
+        for (int i = 0; i < 64; i++) s[i] = v[i];
+        SKML_FM64_LIST(SKML_FM_X, SKML_FM_B)
+        SKML_FM64_OUT(SKML_FM_O)
+    } else {
+        float s[SKML_FM32_SLOTS];
+#pragma unroll
+        for (int i = 0; i < 32; i++) s[i] = v[i];
+        SKML_FM32_LIST(SKML_FM_X, SKML_FM_B)
+        SKML_FM32_OUT(SKML_FM_O)
+    }
+}
+#undef SKML_FM_X
+#undef SKML_FM_B
+#undef SKML_FM_O
 
 template <int R, typename T>
 __device__ __forceinline__ void sort_regs_oddeven(T (&v)[R]) {
+    if constexpr (SKML_FUSED_MERGE && SKML_SORT4_3IN && std::is_same<T, float>::value && (R == 32 || R == 64)) {
+#pragma unroll
+        for (int b = 0; b < R / 4; b++) sort4_3in(v[4 * b], v[4 * b + 1], v[4 * b + 2], v[4 * b + 3]);
+        __builtin_amdgcn_sched_barrier(0);
+        fused_merge_phases<R>(v);
+        return;
+    }
     constexpr int C = OddEvenNet<R>::kCount;
     constexpr auto net = OddEvenNet<R>::table();
     // Batcher's first two merge levels (5 R / 4 comparators) sort each block of 4 registers

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "skml_fused_merge.hpp"
+#include "skml_halfclean.hpp"
 #include "skml_internal.h"
 
 namespace skml {
@@ -413,8 +414,35 @@ __device__ __forceinline__ void sort_regs(T (&v)[R]) {
     }
 }
 
+// The in-register half-clean stages two at a time in 3-input form (skml_halfclean.hpp): their
+// inputs are bitonic, which lets min3 / med3 / max3 stand for two of a stage pair's eight ops
+// (R = 64: 288 ops per lane for six stages against 384).  The A/B build keeps the plain stages.
+#ifndef SKML_FUSED_HALFCLEAN
+#ifdef SKML_AB
+#define SKML_FUSED_HALFCLEAN 0
+#else
+#define SKML_FUSED_HALFCLEAN 1
+#endif
+#endif
+#ifndef SKML_HALFCLEAN_FENCE
+#define SKML_HALFCLEAN_FENCE 3  // groups of four registers (6 ops each) between scheduling barriers
+#endif
+struct HalfcleanOpsF32 {  // bare ops like ce(float&, float&): nothing canonicalises an operand
+    static constexpr int kFenceGroups = SKML_HALFCLEAN_FENCE;
+    static __device__ __forceinline__ float min2(float a, float b) { return fused_merge_op<0>(a, b, b); }
+    static __device__ __forceinline__ float max2(float a, float b) { return fused_merge_op<1>(a, b, b); }
+    static __device__ __forceinline__ float min3(float a, float b, float c) { return fused_merge_op<2>(a, b, c); }
+    static __device__ __forceinline__ float med3(float a, float b, float c) { return fused_merge_op<3>(a, b, c); }
+    static __device__ __forceinline__ float max3(float a, float b, float c) { return fused_merge_op<4>(a, b, c); }
+    static __device__ __forceinline__ void fence() { __builtin_amdgcn_sched_barrier(0); }
+};
+
 template <int R, typename T>
 __device__ __forceinline__ void halfclean_regs(T (&v)[R]) {
+    if constexpr (SKML_FUSED_HALFCLEAN && std::is_same<T, float>::value) {
+        halfclean_paired<R, halfclean_log2(R), HalfcleanOpsF32>(v);
+        return;
+    }
 #pragma unroll
     for (int d = R >> 1; d >= 1; d >>= 1) {
 #pragma unroll
@@ -525,12 +553,16 @@ __device__ __forceinline__ void compact_regs(const uint32_t (&v)[R], uint32_t (&
 // (_sel: the caller already holds the selector, sel_of(odd) or sel_of_bit of the draw word)
 template <int R, typename T>
 __device__ __forceinline__ void halfclean_regs_compact_sel(T (&v)[R], T (&w)[R / 2], T sel) {
+    if constexpr (SKML_FUSED_HALFCLEAN && std::is_same<T, float>::value) {
+        halfclean_paired<R, halfclean_log2(R) - 1, HalfcleanOpsF32>(v);
+    } else {
 #pragma unroll
-    for (int d = R >> 1; d >= 2; d >>= 1) {
+        for (int d = R >> 1; d >= 2; d >>= 1) {
 #pragma unroll
-        for (int i = 0; i < R; i++) {
-            int j = i ^ d;
-            if (j > i) ce(v[i], v[j]);
+            for (int i = 0; i < R; i++) {
+                int j = i ^ d;
+                if (j > i) ce(v[i], v[j]);
+            }
         }
     }
 #pragma unroll

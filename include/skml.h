@@ -344,6 +344,52 @@ int skml_fixed_times_by(skml_ctx* ctx, void* payload_dev, double x);
 /* Synchronise and read the header; returns its status (SKML_E_NAN as described above). */
 int skml_fixed_info(skml_ctx* ctx, const void* payload_dev, skml_fixed_header* hdr_host);
 
+/* ---- ZipGradient's ZipMLQuantizer (ml/gradient/ZipGradient.scala:61-139): the error-minimising
+ * quantizer that Gradient.compress switches to beside the sketch (ml/gradient/Gradient.scala:18-36).
+ * quantize (ZipGradient.scala:70-129): sort a copy, prefix sums r of the sorted values and t of their
+ * squares, then halve the split list round by round -- a pair of neighbouring ranges stays split
+ * when the squared error of joining it is among the thrNum largest (Sort.selectKthLargest over the
+ * errors and the zeros behind them, ties kept; an odd list's last singleton is dropped) -- until at
+ * most bin_num splits are left; splits[i] = sorted[splitIndex[i + 1]] without dedup, min / max the
+ * first / last sorted value, findZeroIdx, bins[i] = indexOf(x[i]).  The result is an ordinary dense
+ * payload (SKML_DENSE_MAGIC, skml_dense_payload_bytes(n, bin_num) bytes, req_bins = bin_num, the
+ * header's bin_num = the effective count, bin_num or bin_num - 1): decode, decode-sum, timesBy,
+ * getBins, the writeObject stream and the all-gather work on it unchanged.
+ *
+ * The sort is Arrays.sort(double[])'s total order (-0.0 before +0.0) and so bit-exact; the prefix
+ * sums are a fixed tree (DESIGN.md "ZipML"), equal on every run but rounded unlike the reference's
+ * sequential loop in the last bits; given r and t, the split search is the reference's, bit for bit.
+ * n in [2, 2^31 - 1], bin_num in [4, 65536] (2 and 3 always reach thrNum = 0, on which the
+ * reference throws); n <= bin_num runs no round: binNum = n, splits = sorted[1..n-1].  Status:
+ * SKML_E_NAN for a NaN or an infinity in the input (the reference returns garbage); SKML_E_ARG for
+ * the arguments above, a short payload, and an input on which a round keeps every split -- the
+ * reference's loop does not terminate there (an all-equal vector of even length > bin_num, a vector
+ * of mostly exact zeros); SKML_E_OOM when the scratch cannot be allocated (the context stays usable).
+ * The scratch is the context's ZipML workspace, allocated by the call that first needs its size and
+ * kept (grow-only, freed with the context, like the context's other workspaces: allocating 9.7 GB
+ * afresh costs the driver about half a second): skml_zip_workspace_bytes(n, fp64) bytes, about 36
+ * bytes per value for fp32 input and 44 for fp64 (0 for an n the encode refuses).  x_dev 16-byte
+ * aligned, payload_dev 256-byte aligned.  Synchronising (the loop's trip count depends on the data).
+ * Timed (skml_ctx_set_timing) as SKML_K_SUMMARY for sort, prefix sums and split search (the rounds'
+ * host read-backs included) and SKML_K_QUANTIZE for the quantize pass. */
+size_t skml_zip_workspace_bytes(int64_t n, int32_t fp64); /* scratch a call over n values needs */
+int skml_zip_encode_f32(skml_ctx* ctx, const float* x_dev, int64_t n, int32_t bin_num, void* payload_dev,
+                        size_t payload_cap);
+int skml_zip_encode_f64(skml_ctx* ctx, const double* x_dev, int64_t n, int32_t bin_num, void* payload_dev,
+                        size_t payload_cap);
+/* Test hooks, not part of the codec: the sorted copy (n doubles) and the two prefix sums exactly as
+ * the encode computes them (the same code).  r_dev and t_dev may both be NULL: the sort alone.
+ * Synchronising; SKML_E_NAN as the encode. */
+int skml_debug_zip_prefix_f32(skml_ctx* ctx, const float* x_dev, int64_t n, double* sorted_dev, double* r_dev,
+                              double* t_dev);
+int skml_debug_zip_prefix_f64(skml_ctx* ctx, const double* x_dev, int64_t n, double* sorted_dev, double* r_dev,
+                              double* t_dev);
+/* Frees the context's ZipML workspace (waits for the stream first); the next encode allocates it
+ * again.  For a caller that encoded one large gradient and wants the memory back. */
+int skml_zip_release_workspace(skml_ctx* ctx);
+/* Test hook: the halving rounds of the context's last successful skml_zip_encode_* (-1: no context). */
+int skml_debug_zip_rounds(skml_ctx* ctx);
+
 /* ---- Host memory in and out (the JNI path: a JVM float[] on its way to a socket) ---- */
 
 /* Pinned host memory (hipHostMalloc): a Java direct ByteBuffer over it (JNI NewDirectByteBuffer)

@@ -138,6 +138,13 @@ _SIGS = {
     "skml_fixed_codes_i32": (C.c_int, [vp, vp, vp, i64]),
     "skml_fixed_times_by": (C.c_int, [vp, vp, C.c_double]),
     "skml_fixed_info": (C.c_int, [vp, vp, C.POINTER(FixedHeader)]),
+    "skml_zip_workspace_bytes": (C.c_size_t, [i64, i32]),
+    "skml_zip_encode_f32": (C.c_int, [vp, vp, i64, i32, vp, C.c_size_t]),
+    "skml_zip_encode_f64": (C.c_int, [vp, vp, i64, i32, vp, C.c_size_t]),
+    "skml_debug_zip_prefix_f32": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    "skml_debug_zip_prefix_f64": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    "skml_debug_zip_rounds": (C.c_int, [vp]),
+    "skml_zip_release_workspace": (C.c_int, [vp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
     "skml_host_free": (C.c_int, [vp]),
     "skml_dense_encode_host_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), vp, C.c_size_t, szp]),

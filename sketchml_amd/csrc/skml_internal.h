@@ -212,6 +212,51 @@ hipError_t launch_fixed_decode_sum(hipStream_t st, const void* payloads, int P, 
                                    int64_t n, double scale, int bits);
 hipError_t launch_fixed_codes(hipStream_t st, const void* payload, int32_t* codes, int64_t n);
 hipError_t launch_fixed_times_by(hipStream_t st, void* payload, double x);
+// ---- ZipMLQuantizer (skml_zip.hip) ----
+constexpr int kZipMinBins = 4;   // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
+constexpr int kZipTail = 4096;   // splitNum at which the rounds move into one workgroup's LDS
+enum : int { kZipOk = 0, kZipThrZero = 1, kZipNoProgress = 2 };
+// Device state of one call: the select's walk, the round's result, the search's outcome.
+struct ZipState {
+    uint64_t prefix;  // digits of the threshold's key fixed so far
+    int64_t k;        // rank (from the largest) still looked for among the candidates
+    double thr;       // the round's threshold
+    int64_t kept;     // pairs the round kept
+    int32_t bad;      // a NaN or an infinity in the input
+    int32_t status;   // kZipOk / kZipThrZero / kZipNoProgress (k_zip_finish)
+    int32_t bin_num;  // the final splitNum
+    int32_t rounds;   // rounds run by k_zip_finish
+    double mn, mx;
+    uint32_t hist[256];
+};
+struct ZipScratch {
+    ZipState* state;
+    void* keys_a;  // uint32 (fp32 input) or uint64 keys, ping-pong
+    void* keys_b;
+    int32_t* idx_a;  // splitIndex ping-pong, over the keys
+    int32_t* idx_b;
+    double* sorted;
+    double* r;
+    double* t;
+    double* err;
+    uint32_t* hist;  // sort: 256 x tiles digit counts, scanned in place
+    uint32_t* hist_tmp;
+    uint32_t* blockcnt;
+    uint32_t* blockcnt_tmp;
+    double* tot_a;  // prefix sums: workgroup totals of every tree level
+    double* tot_b;
+    double* splits;
+};
+size_t zip_scratch_layout(int64_t n, int wide, int own_prefix, ZipScratch* out, char* base);
+// s.state zeroed by the caller; its `bad` flag reports a NaN or an infinity
+hipError_t launch_zip_sort(hipStream_t st, const void* x, int wide, int64_t n, const ZipScratch& s, double* sorted);
+hipError_t launch_zip_scan(hipStream_t st, const double* sorted, int64_t n, double* r, double* t, const ZipScratch& s);
+// one round over idx (null: the identity) into idx_out; s.state->kept then holds the kept pairs
+hipError_t launch_zip_round(hipStream_t st, const int32_t* idx, int32_t* idx_out, int64_t split_num, int64_t n,
+                            int bins, const double* r, const double* t, const ZipScratch& s);
+// the rounds from split_num <= kZipTail on (or none), then s.splits and s.state's outcome
+hipError_t launch_zip_finish(hipStream_t st, const int32_t* idx, int64_t split_num, int64_t n, int bins,
+                             const double* r, const double* t, const double* sorted, const ZipScratch& s);
 // ---- kernel launchers (skml_f64.hip) ----
 hipError_t launch_summary64(hipStream_t st, const double* x, int64_t n, const LeafPartial64* part, int64_t nparts,
                             const double* roots, const int64_t* ranks, int req_bins, int dedup, void* payload,

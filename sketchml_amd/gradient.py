@@ -16,7 +16,7 @@ import torch
 
 from . import fixed_point
 from .exceptions import SketchMLException
-from .quantization import QuantileQuantizer
+from .quantization import QuantileQuantizer, ZipMLQuantizer
 from .sparse import encode_sparse, to_sparse
 
 EPS = 1e-8  # ml/util/Maths.scala:8
@@ -27,6 +27,7 @@ class Kind(Enum):
     SparseDouble = "SparseDouble"
     Sketch = "Sketch"
     FixedPoint = "FixedPoint"
+    Zip = "Zip"
 
 
 def _jint(x: int) -> int:
@@ -246,6 +247,63 @@ class FixedPointGradient:
         return Kind.FixedPoint
 
 
+class ZipGradient:
+    """ml/gradient/ZipGradient.scala:11-58: the ZipMLQuantizer over all values of a dense gradient or
+    over the values of a sparse one, whose indices it keeps as they are.  toDense / toSparse return
+    getValues()[bin] in double."""
+
+    def __init__(self, grad=None, binNum: int = 256, dim: int | None = None):
+        self.binNum = int(binNum)
+        self.dim = int(dim if dim is not None else (grad.dim if grad is not None else 0))
+        self.size = 0
+        self.indices: torch.Tensor | None = None
+        self.quantizer: ZipMLQuantizer | None = None
+        if grad is not None:
+            if grad.kind() == Kind.DenseDouble:
+                self.fromDense(grad)
+            elif grad.kind() == Kind.SparseDouble:
+                self.fromSparse(grad)
+            else:
+                raise SketchMLException(f"Cannot create {Kind.Zip.value} from {grad.kind().value}")
+
+    def _from_array(self, values: torch.Tensor) -> None:
+        self.size = int(values.numel())
+        self.quantizer = ZipMLQuantizer(self.binNum)
+        self.quantizer.quantize(values)
+
+    def fromDense(self, dense: DenseDoubleGradient) -> None:
+        self._from_array(dense.values)
+
+    def fromSparse(self, sparse: SparseDoubleGradient) -> None:
+        self.indices = sparse.indices
+        self._from_array(sparse.values)
+
+    def timesBy(self, x: float) -> None:
+        self.quantizer.timesBy(x)
+
+    def countNNZ(self) -> int:
+        return self.size
+
+    def _values(self) -> torch.Tensor:
+        bins = self.quantizer.getBins()
+        lut = torch.from_numpy(np.ascontiguousarray(self.quantizer.getValues())).to(bins.device)
+        return lut[bins.long()]
+
+    def toDense(self) -> DenseDoubleGradient:
+        return DenseDoubleGradient(self.dim, self._values())
+
+    def toSparse(self) -> SparseDoubleGradient:
+        if self.indices is None:
+            raise SketchMLException("toSparse of a dense ZipGradient: indices is null")
+        return SparseDoubleGradient(self.dim, self.indices, self._values())
+
+    def toAuto(self):
+        return (self.toDense() if self.indices is None else self.toSparse()).toAuto()
+
+    def kind(self) -> Kind:
+        return Kind.Zip
+
+
 def compress(grad, compressor: str = "Sketch", **conf):
     """Gradient.compress's switch (ml/gradient/Gradient.scala:18-36) over MLConf's compressor names
     ("Sketch", "FixedPoint", "None"; case and underscores are ignored, so "fixed_point" works).
@@ -261,6 +319,7 @@ def compress(grad, compressor: str = "Sketch", **conf):
     if name == "none":
         return grad
     if name in ("zip", "float"):
-        raise SketchMLException(f"Compressor not built here: {compressor} (ZipGradient's quantizer is sequential, "
-                                f"the Float codec is a cast; DESIGN.md section 9)")
+        raise SketchMLException(f"Compressor not built here: {compressor} (the Zip codec itself is built: construct "
+                                f"ZipGradient(grad, quantBinNum), only this switch is left; the Float codec is a cast; "
+                                f"DESIGN.md section 9)")
     raise SketchMLException(f"Unrecognizable compressor: {compressor}")

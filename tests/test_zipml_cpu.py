@@ -1,5 +1,6 @@
 """ZipMLQuantizer without a GPU: known answers of the numpy restatement (tests/zipml_ref.py), the
-Python surface, and the round arithmetic the kernels share (sketchml_amd/csrc/skml_zip.hpp) driven
+Python surface, the numpy model of the device's prefix-sum tree (tests/zip_scan_model.py) against exact
+sums, and the round arithmetic the kernels share (sketchml_amd/csrc/skml_zip.hpp) driven
 by a host loop against a sequential implementation, under the address and undefined-behaviour
 sanitizers, as a stand-alone program (tests/zip_check.cpp)."""
 import os
@@ -9,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests import zip_scan_model as M
 from tests import zipml_ref as Z
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,6 +70,59 @@ def test_no_progress_and_thr_zero():
     x = np.random.default_rng(1).standard_normal(1000)
     for bins in (2, 3):
         assert Z.quantize(x, bins).status == Z.THR_ZERO
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _scan_input(name, n):
+    """The inputs of tests/test_gpu_zipml.py's _gauss, and the two with long runs of equal values."""
+    if name == "mostly_zeros":
+        return Z.mostly_zeros(n, 1)
+    x = np.random.default_rng(1000 + n).standard_normal(n) * 1e-3
+    if name == "bf16":
+        return Z.bf16_rounded(x.astype(np.float32))
+    return x.astype(np.float32) if name == "f32" else x
+
+
+@pytest.mark.parametrize("name,n", [(k, n) for n in (257, 2049, 4097, 65539) for k in ("f32", "f64")]
+                         + [("mostly_zeros", 65539), ("bf16", 65539)])
+def test_scan_tree_model_gives_the_correctly_rounded_sums(name, n):
+    """The tree of k_zip_scan_dd in numpy (hi + lo pairs, exact squares) against the exact sums in
+    Python integers rounded once: equal at every index, r and t, which is what the GPU tests ask of
+    the kernel on these inputs.  The same tree in plain double is not (nor is np.cumsum), so that
+    test tells a tree that lost its low parts from one that kept them."""
+    s = Z.java_sort(_scan_input(name, n).astype(np.float64))
+    r, t = M.scan(s)
+    er, et = M.exact_prefix_sums(s)
+    assert np.array_equal(_bits(r), _bits(er)) and np.array_equal(_bits(t), _bits(et))
+    pr, pt = M.scan(s, M.zdd_add_plain)
+    cr, ct = Z.prefix_sums(s)
+    if name in ("f32", "bf16"):  # 24-bit values: small sums of them are exact in any order, the squares' are not
+        assert not np.array_equal(_bits(pt), _bits(et)) and not np.array_equal(_bits(ct), _bits(et))
+    else:
+        assert not np.array_equal(_bits(pr), _bits(er)) and not np.array_equal(_bits(pt), _bits(et))
+        assert not np.array_equal(_bits(cr), _bits(er)) and not np.array_equal(_bits(ct), _bits(et))
+    if name == "mostly_zeros":
+        run = np.nonzero(s == 0)[0]
+        assert len(run) == 58968 and run[-1] - run[0] + 1 == len(run)
+        assert len(np.unique(_bits(r[run]))) == 1 and len(np.unique(_bits(t[run]))) == 1
+
+
+def test_scan_tree_model_pieces():
+    """Exact squares (p + e = v * v in integers), exact sums by hand, and the model on integers, where
+    every order gives np.cumsum."""
+    v = np.random.default_rng(7).standard_normal(1000) * 1e-3
+    p, e = M.two_square(v)
+    vi = M.as_ints(v, -140)
+    assert np.array_equal(M.as_ints(p, -280) + M.as_ints(e, -280), vi * vi) and np.array_equal(p, v * v)
+    r, t = M.exact_prefix_sums(np.array([1.0, 2.0 ** -53, 2.0 ** -53, 2.0 ** -53]))
+    assert r.tolist() == [1.0, 1.0, 1.0 + 2.0 ** -52, 1.0 + 2.0 ** -51]  # ties to even: 1 + 1/2 ulp down, 1 + 3/2 ulp up
+    assert t.tolist() == [1.0, 1.0, 1.0, 1.0]
+    x = np.sort(np.random.default_rng(3).permutation(np.arange(-(1 << 17), 1 << 17))[:5000].astype(np.float64))
+    r, t = M.scan(x)
+    assert np.array_equal(_bits(r), _bits(np.cumsum(x))) and np.array_equal(_bits(t), _bits(np.cumsum(x * x)))
 
 
 def test_python_surface():

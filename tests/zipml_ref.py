@@ -87,6 +87,14 @@ def mostly_zeros(n: int = 4097, seed: int = 1) -> np.ndarray:
     return x
 
 
+def bf16_rounded(x: np.ndarray) -> np.ndarray:
+    """The finite fp32 values rounded to bfloat16 (to nearest even) and widened back: a gradient that
+    went through a 16-bit format, with its many equal values and 8-bit significands."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    u = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    return u.view(np.float32)
+
+
 def prefix_sums(sorted_values: np.ndarray):
     """The reference's sequential loops (ZipGradient.scala:76-83)."""
     s = np.asarray(sorted_values, dtype=np.float64)

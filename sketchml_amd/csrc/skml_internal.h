@@ -1,4 +1,4 @@
-// skml_internal.h -- constants and launch interfaces shared by skml_api.cpp and the kernels.
+// skml_internal.h -- constants and launch interfaces shared by the host files (*.cpp) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

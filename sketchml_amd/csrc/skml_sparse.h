@@ -380,21 +380,4 @@ hipError_t launch_rd_stream(hipStream_t st, const uint8_t* stream, const RdBitSe
 hipError_t launch_rd_words(hipStream_t st, const uint8_t* stream, const int64_t* pos, const int64_t* wpre, int nsec,
                            int64_t total_words, uint64_t* words);
 
-// ---- context services (skml_api.cpp) ----
-hipStream_t ctx_stream(skml_ctx* c);
-// the context's side stream (a high-priority child context) and two events for a fork / join
-int ctx_side_fork(skml_ctx* c, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
-// the side context itself (its stream is ctx_side_fork's `side`; nullptr before the first fork)
-skml_ctx* ctx_side_ctx(skml_ctx* c);
-int ctx_device(skml_ctx* c);
-// grow-only device scratch buffer `slot` (< kScratchSlots) of at least `bytes`; null on failure
-constexpr int kScratchSlots = 24;
-void* ctx_scratch(skml_ctx* c, int slot, size_t bytes);
-// pinned host staging of at least `bytes`
-void* ctx_pinned(skml_ctx* c, size_t bytes);
-// the context's coherent, device-mapped host word (nullptr if it cannot be allocated)
-int64_t* ctx_host_word(skml_ctx* c);
-int set_error(int code, const char* msg);
-bool ctx_timing(skml_ctx* c);
-
 }  // namespace skml

@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -17,29 +16,11 @@
 #include <tuple>
 #include <vector>
 
-#include "skml_internal.h"
-#include "skml_sparse.h"
+#include "skml_host.hpp"
 
 using namespace skml;
 
 namespace {
-
-int sfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
-#define SP_HIP(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return sfail(SKML_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                         __FILE__, __LINE__);                                                \
-    } while (0)
 
 // scratch slots (device)
 enum {
@@ -109,7 +90,7 @@ int group_edges(int32_t zero, int32_t bins, int32_t G, int32_t* edges) {
     }
     const int32_t bpg = bins / G;
     if (zero < bpg) edges[0] = zero;
-    else if (bpg == 0) return sfail(SKML_E_ARG, "calGroupEdges: / by zero (bin_num %d < group_num %d)", bins, G);
+    else if (bpg == 0) return fail(SKML_E_ARG, "calGroupEdges: / by zero (bin_num %d < group_num %d)", bins, G);
     else if ((zero % bpg) < (bpg / 2)) edges[0] = bpg + zero % bpg;
     else edges[0] = zero % bpg;
     for (int32_t i = 1; i < G - 1; i++) edges[i] = edges[i - 1] + bpg;
@@ -358,17 +339,17 @@ void sparse_release(skml_sparse* s) {
 // The host table is edited between uploads, so each upload completes before returning.
 int upload_groups(skml_ctx* c, skml_sparse* s) {
     for (int g = 0; g < kMaxGroups; g++) s->g.inv_cols[g] = s->g.cols[g] > 0 ? 1.0 / (double)s->g.cols[g] : 0.0;
-    SP_HIP(hipMemcpyAsync(s->g_dev, &s->g, sizeof(SpGroups), hipMemcpyHostToDevice, ctx_stream(c)));
-    SP_HIP(hipStreamSynchronize(ctx_stream(c)));
+    HIP_TRY(hipMemcpyAsync(s->g_dev, &s->g, sizeof(SpGroups), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SKML_OK;
 }
 
 int sync_to_host(skml_ctx* c, void* dst, const void* src, size_t bytes) {
     if (!bytes) return SKML_OK;
     void* pin = ctx_pinned(c, bytes);
-    if (!pin) return sfail(SKML_E_OOM, "pinned staging of %zu bytes", bytes);
-    SP_HIP(hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, ctx_stream(c)));
-    SP_HIP(hipStreamSynchronize(ctx_stream(c)));
+    if (!pin) return fail(SKML_E_OOM, "pinned staging of %zu bytes", bytes);
+    HIP_TRY(hipMemcpyAsync(pin, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     std::memcpy(dst, pin, bytes);
     return SKML_OK;
 }
@@ -377,7 +358,7 @@ int sync_to_host(skml_ctx* c, void* dst, const void* src, size_t bytes) {
 // there.  The stream is checked every few thousand polls, so a failed launch cannot hang the caller.
 int wait_host_count(skml_ctx* c, const int64_t* word, int64_t* out) {
     const volatile int64_t* w = word;
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     for (uint64_t k = 1;; k++) {
         const int64_t v = *w;
         if (v >= 0) {
@@ -388,11 +369,11 @@ int wait_host_count(skml_ctx* c, const int64_t* word, int64_t* out) {
             const hipError_t e = hipStreamQuery(st);
             if (e == hipSuccess) {  // the stream has drained: the publishing store is visible now
                 const int64_t v2 = *w;
-                if (v2 < 0) return sfail(SKML_E_HIP, "the compaction did not publish its count");
+                if (v2 < 0) return fail(SKML_E_HIP, "the compaction did not publish its count");
                 *out = v2;
                 return SKML_OK;
             }
-            if (e != hipErrorNotReady) return sfail(SKML_E_HIP, "stream failed: %s", hipGetErrorString(e));
+            if (e != hipErrorNotReady) return fail(SKML_E_HIP, "stream failed: %s", hipGetErrorString(e));
         }
         __builtin_ia32_pause();
     }
@@ -400,7 +381,7 @@ int wait_host_count(skml_ctx* c, const int64_t* word, int64_t* out) {
 
 // Exclusive column scans of a [tiles][K] table; column totals copied to `totals` (host).
 int scan_tiles(skml_ctx* c, uint64_t* sums, int64_t tiles, int K, uint64_t* totals) {
-    SP_HIP(launch_scan_cols(ctx_stream(c), sums, tiles, K));
+    HIP_TRY(launch_scan_cols(c->stream, sums, tiles, K));
     if (totals) return sync_to_host(c, totals, sums + tiles * K, sizeof(uint64_t) * (size_t)K);
     return SKML_OK;
 }
@@ -417,29 +398,29 @@ int encode_delta_device(skml_ctx* c, hipStream_t st, SpGroups* g_dev, const int3
                         int64_t n, const uint32_t* hist, const uint32_t* err, uint64_t* fw, uint64_t* dw) {
     const int64_t tiles = sp_tiles(n, kSpTile);
     uint64_t* ts = scratch<uint64_t>(c, kSlotTiles, (size_t)(tiles + 1) * 2);
-    if (!ts) return sfail(SKML_E_OOM, "tile sums");
-    SP_HIP(launch_sp_plan_delta(st, g_dev, hist, err));
-    SP_HIP(launch_delta_lens(st, need, n, g_dev, ts));
-    SP_HIP(launch_scan_cols_small(st, ts, tiles, 2));
-    SP_HIP(launch_sp_zero_edges(st, ts, tiles, g_dev, fw, dw));
-    SP_HIP(launch_delta_write(st, gk, need, n, g_dev, ts, fw, dw));
-    SP_HIP(launch_sp_finalize(st, g_dev, ts + tiles * 2));
+    if (!ts) return fail(SKML_E_OOM, "tile sums");
+    HIP_TRY(launch_sp_plan_delta(st, g_dev, hist, err));
+    HIP_TRY(launch_delta_lens(st, need, n, g_dev, ts));
+    HIP_TRY(launch_scan_cols_small(st, ts, tiles, 2));
+    HIP_TRY(launch_sp_zero_edges(st, ts, tiles, g_dev, fw, dw));
+    HIP_TRY(launch_delta_write(st, gk, need, n, g_dev, ts, fw, dw));
+    HIP_TRY(launch_sp_finalize(st, g_dev, ts + tiles * 2));
     return SKML_OK;
 }
 
 int check_params(const skml_params* p) {
-    if (!p) return sfail(SKML_E_ARG, "params is NULL");
+    if (!p) return fail(SKML_E_ARG, "params is NULL");
     if (p->bin_num < 2 || p->bin_num > SKML_MAX_BINS)
-        return sfail(SKML_E_ARG, "bin_num %d outside [2, %d]", p->bin_num, SKML_MAX_BINS);
+        return fail(SKML_E_ARG, "bin_num %d outside [2, %d]", p->bin_num, SKML_MAX_BINS);
     if (p->group_num < 2 || p->group_num > kMaxGroups)
-        return sfail(SKML_E_ARG, "group_num %d outside [2, %d]", p->group_num, kMaxGroups);
+        return fail(SKML_E_ARG, "group_num %d outside [2, %d]", p->group_num, kMaxGroups);
     if (p->row_num < 1 || p->row_num > kMaxRows)
-        return sfail(SKML_E_ARG, "Currently only %d hash functions are available", kMaxRows);
-    if (!(p->col_ratio > 0.0)) return sfail(SKML_E_ARG, "col_ratio must be positive");
+        return fail(SKML_E_ARG, "Currently only %d hash functions are available", kMaxRows);
+    if (!(p->col_ratio > 0.0)) return fail(SKML_E_ARG, "col_ratio must be positive");
     if (p->quant_type != SKML_QUANTILE && p->quant_type != SKML_UNIFORM)
-        return sfail(SKML_E_ARG, "Unrecognizable quantization type: %d", p->quant_type);
+        return fail(SKML_E_ARG, "Unrecognizable quantization type: %d", p->quant_type);
     if (p->parallelism < 0 || p->parallelism > 65536)
-        return sfail(SKML_E_ARG, "Invalid parallelism: %d", p->parallelism);
+        return fail(SKML_E_ARG, "Invalid parallelism: %d", p->parallelism);
     return SKML_OK;
 }
 
@@ -454,9 +435,9 @@ static std::atomic<int> g_fail_cellbuf{0};
 
 int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int64_t nnz, const skml_params* p,
               skml_sparse** out) {
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     skml_sparse* s = new skml_sparse();
-    s->device = ctx_device(c);
+    s->device = c->device;
     s->nnz = nnz;
     s->params = *p;
     hipStream_t side = nullptr;  // the DeltaAdaptive chain's stream, once forked
@@ -469,12 +450,12 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
 #define SP_TRY(expr)                                                                                    \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return bail(sfail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
+        if (e_ != hipSuccess) return bail(fail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
     } while (0)
     const int G = p->group_num, rows = p->row_num;
     // ---- the payload's device block, sized for the worst case (no count has to come back first) ----
     const double cols_all = std::ceil((double)nnz * p->col_ratio);
-    if (cols_all * rows > 4.0e12) return bail(sfail(SKML_E_OOM, "MinMaxSketch tables of colRatio %g", p->col_ratio));
+    if (cols_all * rows > 4.0e12) return bail(fail(SKML_E_OOM, "MinMaxSketch tables of colRatio %g", p->col_ratio));
     const int64_t cells_max = nnz > 0 ? (int64_t)rows * ((int64_t)cols_all + 2 * G + 2) : 0;
     const int64_t fwn = flag_words_max(nnz), dwn = delta_words_max(nnz);
     s->qbytes = skml_dense_payload_bytes(nnz, p->bin_num);
@@ -489,7 +470,7 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
     const size_t o_qv = o_dw + align_up(sizeof(uint64_t) * (size_t)dwn, 256);
     const size_t total = o_qv + sizeof(double) * (size_t)p->bin_num;
     char* blk = static_cast<char*>(block_get(s->device, total, &s->block_cap));
-    if (!blk) return bail(sfail(SKML_E_OOM, "sparse payload of %zu bytes", total));
+    if (!blk) return bail(fail(SKML_E_OOM, "sparse payload of %zu bytes", total));
     s->block = blk;
     s->qpayload = blk;
     s->qv_dev = reinterpret_cast<double*>(blk + o_qv);
@@ -535,11 +516,11 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
     SP_TRY(launch_sp_plan_edges(st, s->qpayload, init, s->g_dev));
     const int64_t tiles = sp_tiles(nnz, kSpTile);
     uint64_t* tc = scratch<uint64_t>(c, kSlotTiles, (size_t)(tiles + 1) * G);
-    if (!tc) return bail(sfail(SKML_E_OOM, "tile counts"));
+    if (!tc) return bail(fail(SKML_E_OOM, "tile counts"));
     // partition counts; the grid also zeroes the histogram, error flag and bucket counters below
     uint64_t* bucket = scratch<uint64_t>(c, kSlotCells, (size_t)2 * nbuckets + 2);  // counts->bases, cursors
     uint32_t* small = scratch<uint32_t>(c, kSlotSmall, (size_t)kMaxGroups * kDeltaHist + 64);
-    if (!bucket || !small) return bail(sfail(SKML_E_OOM, "sparse scratch"));
+    if (!bucket || !small) return bail(fail(SKML_E_OOM, "sparse scratch"));
     SP_TRY(launch_part_count(st, s->qpayload, nnz, s->g_dev, tc, small, (int64_t)kMaxGroups * kDeltaHist + 64, bucket,
                              (int64_t)2 * nbuckets + 2));
     SP_TRY(launch_scan_cols_major(st, tc, tiles, G));
@@ -552,7 +533,7 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
     const size_t npairs = (size_t)rows * (size_t)nnz + (tile_off ? (size_t)15 * mm_tiles * nbuckets : 0);
     const size_t npairs32 = (size_t)rows * (size_t)nnz + (tile_off ? (size_t)31 * mm_tiles * nbuckets : 0);
     uint64_t* pairs = scratch<uint64_t>(c, kSlotDelta, std::max(npairs, (npairs32 + 1) / 2));
-    if (!gk || !gb || !need || !pairs) return bail(sfail(SKML_E_OOM, "sparse scratch"));
+    if (!gk || !gb || !need || !pairs) return bail(fail(SKML_E_OOM, "sparse scratch"));
     uint64_t* cursor = bucket + nbuckets + 1;
     uint32_t* hist = small;
     uint32_t* err = small + kMaxGroups * kDeltaHist;
@@ -585,21 +566,21 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
     const size_t qh = kHeaderBytes + sizeof(double) * (size_t)(p->bin_num - 1);
     const size_t o_pg = align_up(qh, 256);
     uint8_t* pin = static_cast<uint8_t*>(ctx_pinned(c, o_pg + sizeof(SpGroups)));
-    if (!pin) return bail(sfail(SKML_E_OOM, "pinned staging"));
+    if (!pin) return bail(fail(SKML_E_OOM, "pinned staging"));
     SP_TRY(hipMemcpyAsync(pin, s->qpayload, qh, hipMemcpyDeviceToHost, st));
     SP_TRY(hipMemcpyAsync(pin + o_pg, s->g_dev, sizeof(SpGroups), hipMemcpyDeviceToHost, st));
     SP_TRY(hipStreamSynchronize(st));
 #undef SP_TRY
     std::memcpy(&s->hdr, pin, sizeof(skml_dense_header));
     std::memcpy(&s->g, pin + o_pg, sizeof(SpGroups));
-    if (s->hdr.status == SKML_E_NAN || (s->g.status & kSpNan)) return bail(sfail(SKML_E_NAN, "Encounter NaN value"));
+    if (s->hdr.status == SKML_E_NAN || (s->g.status & kSpNan)) return bail(fail(SKML_E_NAN, "Encounter NaN value"));
     if (s->g.status & kSpEdges) {
         int32_t e_host[kMaxGroups];
         const int e = group_edges(s->hdr.zero_idx, s->hdr.bin_num, G, e_host);
-        return bail(e ? e : sfail(SKML_E_HIP, "group plan disagrees with calGroupEdges"));
+        return bail(e ? e : fail(SKML_E_HIP, "group plan disagrees with calGroupEdges"));
     }
     if (s->g.status & kSpOrder)
-        return bail(sfail(SKML_E_ORDER, "Log for a non-positive key delta (keys must ascend strictly)"));
+        return bail(fail(SKML_E_ORDER, "Log for a non-positive key delta (keys must ascend strictly)"));
     {  // Quantizer.getValues (base/Quantizer.java:39-47)
         const int B = s->hdr.bin_num, ns = B - 1;
         const double* sp = reinterpret_cast<const double*>(pin + kHeaderBytes);
@@ -638,7 +619,7 @@ struct DecodeValues {
 };
 int decode_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, bool query,
                   const DecodeValues* dv = nullptr, const RunBoundsOut* rbo = nullptr) {
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     const SpGroups& G = s->g;
     const int64_t n = s->nnz;
     bool any_unary = false;
@@ -648,19 +629,19 @@ int decode_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, b
         end_pos = scratch<int64_t>(c, kSlotEndPos, (size_t)n);
         const int64_t wt = sp_tiles(s->n_flag_words, kSpTile);
         uint64_t* ts = scratch<uint64_t>(c, kSlotTiles, (size_t)(wt + 1));
-        if (!end_pos || !ts) return sfail(SKML_E_OOM, "decode scratch");
-        SP_HIP(launch_unary_count(st, s->flag_words, s->n_flag_words, s->g_dev, ts));
+        if (!end_pos || !ts) return fail(SKML_E_OOM, "decode scratch");
+        HIP_TRY(launch_unary_count(st, s->flag_words, s->n_flag_words, s->g_dev, ts));
         if (int e = scan_tiles(c, ts, wt, 1, nullptr)) return e;
-        SP_HIP(launch_unary_select(st, s->flag_words, s->n_flag_words, s->g_dev, ts, end_pos));
+        HIP_TRY(launch_unary_select(st, s->flag_words, s->n_flag_words, s->g_dev, ts, end_pos));
     }
     const int64_t tiles = sp_tiles(n, kSpTile);
     uint64_t* ts = scratch<uint64_t>(c, kSlotTiles, (size_t)(tiles + 1) * 2);
     uint64_t* gpre = scratch<uint64_t>(c, kSlotSmall, kMaxGroups + 8);
-    if (!ts || !gpre) return sfail(SKML_E_OOM, "decode scratch");
+    if (!ts || !gpre) return fail(SKML_E_OOM, "decode scratch");
     uint64_t* ts2 = ts + (tiles + 1);
     uint8_t* dlen = scratch<uint8_t>(c, kSlotNeed, (size_t)n);
     uint32_t* delta = scratch<uint32_t>(c, kSlotDelta, (size_t)n);
-    if (!dlen || !delta) return sfail(SKML_E_OOM, "decode scratch");
+    if (!dlen || !delta) return fail(SKML_E_OOM, "decode scratch");
     // the query gathers from a byte (binNum <= 256) or 16-bit image of the tables, built by extra
     // blocks of the lengths' launch
     const int32_t* tab = query ? s->tables : nullptr;
@@ -673,7 +654,7 @@ int decode_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, b
     } else if (tab && s->ncells > 0 && (reinterpret_cast<uintptr_t>(tab) & 15) == 0) {
         width = G.bin_num <= 256 ? 8 : 16;  // any width gives the same bins (the sentinel reads back)
         tnar = ctx_scratch(c, kSlotNarrowTab, (size_t)s->ncells * (size_t)(width / 8));
-        if (!tnar) return sfail(SKML_E_OOM, "decode scratch (table image)");
+        if (!tnar) return fail(SKML_E_OOM, "decode scratch (table image)");
     }
     // three passes (lengths, their tile scan, deltas); SKML_FORM_DEC_LOOKBACK = 1: one pass with
     // decoupled look-backs for the bit offsets and the deltas' prefixes, 2: the same pass with the
@@ -686,25 +667,25 @@ int decode_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, b
     constexpr int split = 1;
 #endif
     if (split == 1) {
-        SP_HIP(launch_dec_lens(st, s->flag_words, s->n_flag_words, end_pos, n, s->g_dev, dlen, ts,
-                               NarrowJob{tab, s->ncells, tab ? tnar : nullptr, width}));
+        HIP_TRY(launch_dec_lens(st, s->flag_words, s->n_flag_words, end_pos, n, s->g_dev, dlen, ts,
+                                NarrowJob{tab, s->ncells, tab ? tnar : nullptr, width}));
         if (int e = scan_tiles(c, ts, tiles, 1, nullptr)) return e;
-        SP_HIP(launch_dec_deltas(st, s->delta_words, s->n_delta_words, dlen, n, s->g_dev, ts, delta, ts2));
+        HIP_TRY(launch_dec_deltas(st, s->delta_words, s->n_delta_words, dlen, n, s->g_dev, ts, delta, ts2));
     } else {
 #ifdef SKML_AB
         uint64_t* status = scratch<uint64_t>(c, kSlotLookback, 2 * (size_t)tiles + 8);
-        if (!status) return sfail(SKML_E_OOM, "decode scratch (look-back)");
-        SP_HIP(launch_dec_lens_deltas(st, s->flag_words, s->n_flag_words, end_pos, n, s->g_dev, s->delta_words,
-                                      s->n_delta_words, delta, ts2, status, NarrowJob{tab, s->ncells, tab ? tnar : nullptr, width},
-                                      split == 0));
+        if (!status) return fail(SKML_E_OOM, "decode scratch (look-back)");
+        HIP_TRY(launch_dec_lens_deltas(st, s->flag_words, s->n_flag_words, end_pos, n, s->g_dev, s->delta_words,
+                                       s->n_delta_words, delta, ts2, status, NarrowJob{tab, s->ncells, tab ? tnar : nullptr, width},
+                                       split == 0));
 #endif
     }
     if (split != 0)
         if (int e = scan_tiles(c, ts2, tiles, 1, nullptr)) return e;
-    SP_HIP(launch_group_prefix(st, delta, n, s->g_dev, G.G, ts2, gpre));
-    SP_HIP(launch_dec_keys(st, delta, n, s->g_dev, G, ts2, gpre, tab, tnar, width, gk, gb, dv ? dv->nq : 0,
-                           dv ? dv->gb : nullptr, dv ? dv->bw : 0, dv ? dv->err : nullptr,
-                           dv ? dv->rb : rbo ? *rbo : RunBoundsOut{nullptr, 0, 0, 0}));
+    HIP_TRY(launch_group_prefix(st, delta, n, s->g_dev, G.G, ts2, gpre));
+    HIP_TRY(launch_dec_keys(st, delta, n, s->g_dev, G, ts2, gpre, tab, tnar, width, gk, gb, dv ? dv->nq : 0,
+                            dv ? dv->gb : nullptr, dv ? dv->bw : 0, dv ? dv->err : nullptr,
+                            dv ? dv->rb : rbo ? *rbo : RunBoundsOut{nullptr, 0, 0, 0}));
     return SKML_OK;
 }
 
@@ -712,16 +693,16 @@ int decode_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, b
 // merges on the device; keys and bins land in keys_out / bins_out.
 int merge_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, int32_t* keys_out,
                  int32_t* bins_out) {
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     const int64_t n = s->nnz;
     const SpGroups& G = s->g;
     int32_t* k1 = scratch<int32_t>(c, kSlotK1, (size_t)n);
     int32_t* b1 = scratch<int32_t>(c, kSlotB1, (size_t)n);
-    if (!k1 || !b1) return sfail(SKML_E_OOM, "merge scratch");
+    if (!k1 || !b1) return fail(SKML_E_OOM, "merge scratch");
     // every round's run offsets (the rounds halve the run count) go to the kernels by value
     std::vector<int64_t> rs(G.gstart, G.gstart + G.G + 1);
     int64_t* split = rs.size() > 2 ? scratch<int64_t>(c, kSlotEndPos, (size_t)sp_tiles(n, kSpTile) + 2) : nullptr;
-    if (rs.size() > 2 && !split) return sfail(SKML_E_OOM, "merge split points");
+    if (rs.size() > 2 && !split) return fail(SKML_E_OOM, "merge split points");
     int32_t *kin = gk, *bin = gb, *kout = k1, *bout = b1;
     // the last round writes straight into the outputs (bins too unless bins_out is a scratch buffer)
     const bool bins_direct = bins_out && bins_out != gb && bins_out != b1;
@@ -730,7 +711,7 @@ int merge_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, in
         const bool last = rs.size() <= 3;
         int32_t* ko = last ? keys_out : kout;
         int32_t* bo = last && bins_direct ? bins_out : bout;
-        SP_HIP(launch_merge_round(st, kin, bin, ko, bo, rs.data(), (int)rs.size() - 1, n, split));
+        HIP_TRY(launch_merge_round(st, kin, bin, ko, bo, rs.data(), (int)rs.size() - 1, n, split));
         std::vector<int64_t> nx;
         for (size_t i = 0; i < rs.size(); i += 2) nx.push_back(rs[i]);
         if (nx.back() != rs.back()) nx.push_back(rs.back());
@@ -742,9 +723,9 @@ int merge_groups(skml_ctx* c, const skml_sparse* s, int32_t* gk, int32_t* gb, in
         kout = kin == k1 ? gk : k1;
         bout = bin == b1 ? gb : b1;
     }
-    if (!keys_done) SP_HIP(hipMemcpyAsync(keys_out, kin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (!keys_done) HIP_TRY(hipMemcpyAsync(keys_out, kin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
     if (!bins_done && bins_out && bins_out != bin)
-        SP_HIP(hipMemcpyAsync(bins_out, bin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(bins_out, bin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
     return SKML_OK;
 }
 
@@ -769,8 +750,8 @@ int rs_merge_prepare(skml_ctx* c, const skml_sparse* s, RsMerge* m) {
     const size_t o_b = align_up(sizeof(RsInfo), 256);
     char* blk = static_cast<char*>(
         ctx_scratch(c, kSlotRsMerge, o_b + sizeof(int32_t) * (size_t)s->g.G * (size_t)(kRsRanges + 1)));
-    if (!blk) return sfail(SKML_E_OOM, "merge scratch");
-    SP_HIP(hipMemsetAsync(blk, 0, o_b, ctx_stream(c)));  // whole 256-byte units: one fill
+    if (!blk) return fail(SKML_E_OOM, "merge scratch");
+    HIP_TRY(hipMemsetAsync(blk, 0, o_b, c->stream));  // whole 256-byte units: one fill
     m->info = reinterpret_cast<RsInfo*>(blk);
     m->bounds = reinterpret_cast<int32_t*>(blk + o_b);
     return SKML_OK;
@@ -783,11 +764,11 @@ int rs_merge_start(skml_ctx* c, const skml_sparse* s, const RsMerge& m, const in
                    int32_t* keys_out, void* out, int vkind, const double* qv, int nq, volatile unsigned** pending) {
     *pending = nullptr;
     if (!m.info) return SKML_OK;
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     unsigned* pin = static_cast<unsigned*>(ctx_pinned(c, 64));
-    if (!pin) return sfail(SKML_E_OOM, "merge scratch");
-    SP_HIP(launch_rs_merge(st, gk, gb, s->nnz, s->g_dev, m.bounds, m.info, keys_out, out, vkind, qv, nq, m.by_query));
-    SP_HIP(hipMemcpyAsync(pin, &m.info->irregular, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (!pin) return fail(SKML_E_OOM, "merge scratch");
+    HIP_TRY(launch_rs_merge(st, gk, gb, s->nnz, s->g_dev, m.bounds, m.info, keys_out, out, vkind, qv, nq, m.by_query));
+    HIP_TRY(hipMemcpyAsync(pin, &m.info->irregular, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     *pending = pin;
     return SKML_OK;
 }
@@ -806,21 +787,21 @@ template <typename T>
 int compact_any(skml_ctx* c, const T* dense, int64_t dim, int32_t* keys, T* vals, int64_t* nnz_out,
                 bool poll = false) {
     if (!c || !nnz_out || dim < 0 || (dim > 0 && (!dense || !keys || !vals)))
-        return sfail(SKML_E_ARG, "bad compaction arguments");
-    if (dim > (int64_t)INT32_MAX) return sfail(SKML_E_ARG, "dim %lld exceeds Java int keys", (long long)dim);
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+        return fail(SKML_E_ARG, "bad compaction arguments");
+    if (dim > (int64_t)INT32_MAX) return fail(SKML_E_ARG, "dim %lld exceeds Java int keys", (long long)dim);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     const int64_t tiles = sp_tiles(dim, sizeof(T) == 8 ? kCompactTile / 2 : kCompactTile);
     uint64_t* status = scratch<uint64_t>(c, kSlotStatus, (size_t)tiles + 8);
-    if (!status) return sfail(SKML_E_OOM, "compaction status");
+    if (!status) return fail(SKML_E_OOM, "compaction status");
     unsigned* ticket = reinterpret_cast<unsigned*>(status + tiles);
     int64_t* nnz_dev = reinterpret_cast<int64_t*>(status + tiles + 1);
     int64_t* hw = poll && tiles > 0 ? ctx_host_word(c) : nullptr;
     if (hw) *reinterpret_cast<volatile int64_t*>(hw) = -1;
-    SP_HIP(hipMemsetAsync(status, 0, sizeof(uint64_t) * ((size_t)tiles + 8), st));
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint64_t) * ((size_t)tiles + 8), st));
     int64_t* dst = hw ? hw : nnz_dev;
-    if constexpr (sizeof(T) == 8) SP_HIP(launch_compact64(st, dense, dim, keys, vals, status, ticket, dst));
-    else SP_HIP(launch_compact(st, dense, dim, keys, vals, status, ticket, dst));
+    if constexpr (sizeof(T) == 8) HIP_TRY(launch_compact64(st, dense, dim, keys, vals, status, ticket, dst));
+    else HIP_TRY(launch_compact(st, dense, dim, keys, vals, status, ticket, dst));
     if (hw) return wait_host_count(c, hw, nnz_out);
     return sync_to_host(c, nnz_out, nnz_dev, sizeof(int64_t));
 }
@@ -840,33 +821,33 @@ int skml_sparse_compact_f64(skml_ctx* c, const double* dense, int64_t dim, int32
 
 int skml_sparse_encode_kv_f32(skml_ctx* c, const int32_t* keys, const float* vals, int64_t nnz,
                               const skml_params* p, skml_sparse** out) {
-    if (!c || !out || nnz < 0 || (nnz > 0 && (!keys || !vals))) return sfail(SKML_E_ARG, "bad sparse arguments");
-    if (nnz > (int64_t)INT32_MAX) return sfail(SKML_E_ARG, "nnz exceeds Java int");
+    if (!c || !out || nnz < 0 || (nnz > 0 && (!keys || !vals))) return fail(SKML_E_ARG, "bad sparse arguments");
+    if (nnz > (int64_t)INT32_MAX) return fail(SKML_E_ARG, "nnz exceeds Java int");
     if (int e = check_params(p)) return e;
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    HIP_TRY(hipSetDevice(c->device));
     *out = nullptr;
     return encode_kv(c, keys, vals, false, nnz, p, out);
 }
 
 int skml_sparse_encode_kv_f64(skml_ctx* c, const int32_t* keys, const double* vals, int64_t nnz,
                               const skml_params* p, skml_sparse** out) {
-    if (!c || !out || nnz < 0 || (nnz > 0 && (!keys || !vals))) return sfail(SKML_E_ARG, "bad sparse arguments");
-    if (nnz > (int64_t)INT32_MAX) return sfail(SKML_E_ARG, "nnz exceeds Java int");
+    if (!c || !out || nnz < 0 || (nnz > 0 && (!keys || !vals))) return fail(SKML_E_ARG, "bad sparse arguments");
+    if (nnz > (int64_t)INT32_MAX) return fail(SKML_E_ARG, "nnz exceeds Java int");
     if (int e = check_params(p)) return e;
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    HIP_TRY(hipSetDevice(c->device));
     *out = nullptr;
     return encode_kv(c, keys, vals, true, nnz, p, out);
 }
 
 int skml_sparse_encode_f32(skml_ctx* c, const float* dense, int64_t dim, const skml_params* p,
                            skml_sparse** out) {
-    if (!c || !out || dim < 0) return sfail(SKML_E_ARG, "bad sparse arguments");
+    if (!c || !out || dim < 0) return fail(SKML_E_ARG, "bad sparse arguments");
     if (int e = check_params(p)) return e;
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    HIP_TRY(hipSetDevice(c->device));
     const size_t cap = (size_t)std::max<int64_t>(dim, 1);
     int32_t* keys = scratch<int32_t>(c, kSlotCKeys, cap);
     float* vals = scratch<float>(c, kSlotCVals, cap);
-    if (!keys || !vals) return sfail(SKML_E_OOM, "compaction output");
+    if (!keys || !vals) return fail(SKML_E_OOM, "compaction output");
     int64_t nnz = 0;
     if (int e = compact_any<float>(c, dense, dim, keys, vals, &nnz, true)) return e;
     return encode_kv(c, keys, vals, false, nnz, p, out);
@@ -874,13 +855,13 @@ int skml_sparse_encode_f32(skml_ctx* c, const float* dense, int64_t dim, const s
 
 int skml_sparse_encode_f64(skml_ctx* c, const double* dense, int64_t dim, const skml_params* p,
                            skml_sparse** out) {
-    if (!c || !out || dim < 0) return sfail(SKML_E_ARG, "bad sparse arguments");
+    if (!c || !out || dim < 0) return fail(SKML_E_ARG, "bad sparse arguments");
     if (int e = check_params(p)) return e;
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    HIP_TRY(hipSetDevice(c->device));
     const size_t cap = (size_t)std::max<int64_t>(dim, 1);
     int32_t* keys = scratch<int32_t>(c, kSlotCKeys, cap);
     double* vals = scratch<double>(c, kSlotCVals, cap);
-    if (!keys || !vals) return sfail(SKML_E_OOM, "compaction output");
+    if (!keys || !vals) return fail(SKML_E_OOM, "compaction output");
     int64_t nnz = 0;
     if (int e = compact_any<double>(c, dense, dim, keys, vals, &nnz, true)) return e;
     return encode_kv(c, keys, vals, true, nnz, p, out);
@@ -893,25 +874,25 @@ namespace {
 // SparseVectorCompressor.java:118-126) as fp32 or as the reference's doubles
 template <typename T>
 int decode_values(skml_ctx* c, const skml_sparse* s, int32_t* keys_dev, T* vals_dev) {
-    if (!c || !s) return sfail(SKML_E_ARG, "bad decode arguments");
+    if (!c || !s) return fail(SKML_E_ARG, "bad decode arguments");
     const int64_t n = s->nnz;
     if (n == 0) return SKML_OK;
-    if (!keys_dev || !vals_dev) return sfail(SKML_E_ARG, "keys/vals are NULL");
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
-    if (s->qvalues.empty()) return sfail(SKML_E_STATE, "quantValues are not set (deserialised without them)");
+    if (!keys_dev || !vals_dev) return fail(SKML_E_ARG, "keys/vals are NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (s->qvalues.empty()) return fail(SKML_E_STATE, "quantValues are not set (deserialised without them)");
     int32_t* gk = scratch<int32_t>(c, kSlotGKeys, (size_t)n);
     int32_t* gb = scratch<int32_t>(c, kSlotGBins, (size_t)n);
     int32_t* b1 = scratch<int32_t>(c, kSlotB1, (size_t)n);
-    if (!gk || !gb || !b1) return sfail(SKML_E_OOM, "decode scratch");
+    if (!gk || !gb || !b1) return fail(SKML_E_OOM, "decode scratch");
     // the value table's upload and the merge's RsInfo fill go first: the GPU runs them while the
     // decode's kernels are still being queued
     const int nq = (int)s->qvalues.size();
     double* qv = s->qv_dev;  // the payload's device copy (encode / import), or the host table uploaded
     if (!qv || !s->qv_dev_ok) {
         if (!qv) qv = reinterpret_cast<double*>(ctx_scratch(c, kSlotCells, sizeof(double) * s->qvalues.size()));
-        if (!qv) return sfail(SKML_E_OOM, "value table");
-        SP_HIP(hipMemcpyAsync(qv, s->qvalues.data(), sizeof(double) * s->qvalues.size(), hipMemcpyHostToDevice, st));
+        if (!qv) return fail(SKML_E_OOM, "value table");
+        HIP_TRY(hipMemcpyAsync(qv, s->qvalues.data(), sizeof(double) * s->qvalues.size(), hipMemcpyHostToDevice, st));
         if (qv == s->qv_dev) const_cast<skml_sparse*>(s)->qv_dev_ok = true;  // ordered before later restores
     }
     RsMerge rm;
@@ -922,14 +903,14 @@ int decode_values(skml_ctx* c, const skml_sparse* s, int32_t* keys_dev, T* vals_
     // of bounds) fails the decode (the one-pass merge sends such input here too)
     auto rounds = [&]() -> int {
         unsigned* err = scratch<unsigned>(c, kSlotStatus, 64);
-        if (!err) return sfail(SKML_E_OOM, "decode scratch");
-        SP_HIP(hipMemsetAsync(err, 0, sizeof(unsigned), st));
+        if (!err) return fail(SKML_E_OOM, "decode scratch");
+        HIP_TRY(hipMemsetAsync(err, 0, sizeof(unsigned), st));
         if (int e = merge_groups(c, s, gk, gb, keys_dev, b1)) return e;
-        if constexpr (sizeof(T) == 8) SP_HIP(launch_bin_values64(st, b1, n, qv, nq, vals_dev, err));
-        else SP_HIP(launch_bin_values(st, b1, n, qv, nq, vals_dev, err));
+        if constexpr (sizeof(T) == 8) HIP_TRY(launch_bin_values64(st, b1, n, qv, nq, vals_dev, err));
+        else HIP_TRY(launch_bin_values(st, b1, n, qv, nq, vals_dev, err));
         unsigned bad = 0;
         if (int e = sync_to_host(c, &bad, err, sizeof(bad))) return e;
-        return bad ? sfail(SKML_E_ARG, "a restored bin lies outside the %d quantValues", nq) : SKML_OK;
+        return bad ? fail(SKML_E_ARG, "a restored bin lies outside the %d quantValues", nq) : SKML_OK;
     };
     volatile unsigned* pending = nullptr;
     if (int e = rs_merge_start(c, s, rm, gk, gb, keys_dev, vals_dev, sizeof(T) == 8 ? 2 : 1, qv, nq, &pending))
@@ -938,7 +919,7 @@ int decode_values(skml_ctx* c, const skml_sparse* s, int32_t* keys_dev, T* vals_
         t_merge_path = s->g.G < 2 ? 0 : 2;
         return rounds();
     }
-    SP_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     t_merge_path = 1;
     if (*pending) {  // not regular, or a bin outside quantValues: the rounds decide
         t_merge_path = 3;
@@ -959,27 +940,27 @@ int skml_sparse_decode_f64(skml_ctx* c, const skml_sparse* s, int32_t* keys_dev,
 }
 
 int skml_sparse_times_by(skml_sparse* s, double x) {
-    if (!s) return sfail(SKML_E_ARG, "NULL argument");
+    if (!s) return fail(SKML_E_ARG, "NULL argument");
     for (double& v : s->qvalues) v *= x;  // SparseVectorCompressor.timesBy (:128-134)
     s->qv_dev_ok = false;  // the device copy is re-uploaded by the next restore
     return SKML_OK;
 }
 
 int skml_sparse_values(const skml_sparse* s, double* out, int32_t cap) {
-    if (!s || !out) return sfail(SKML_E_ARG, "NULL argument");
+    if (!s || !out) return fail(SKML_E_ARG, "NULL argument");
     const size_t k = std::min<size_t>(s->qvalues.size(), (size_t)std::max(cap, 0));
     std::memcpy(out, s->qvalues.data(), sizeof(double) * k);
     return SKML_OK;
 }
 
 int skml_sparse_nnz(const skml_sparse* s, int64_t* nnz) {
-    if (!s || !nnz) return sfail(SKML_E_ARG, "NULL argument");
+    if (!s || !nnz) return fail(SKML_E_ARG, "NULL argument");
     *nnz = s->nnz;
     return SKML_OK;
 }
 
 int skml_sparse_quant_info(const skml_sparse* s, skml_dense_header* hdr, double* splits_host, int32_t cap) {
-    if (!s || !hdr) return sfail(SKML_E_ARG, "NULL argument");
+    if (!s || !hdr) return fail(SKML_E_ARG, "NULL argument");
     *hdr = s->hdr;
     if (splits_host) {
         const size_t k = std::min<size_t>(s->splits.size(), (size_t)std::max(cap, 0));
@@ -1008,8 +989,8 @@ static int extract_bits(skml_ctx* c, const uint64_t* words, int64_t b0, int64_t 
 
 int skml_sparse_group_info(skml_ctx* c, const skml_sparse* s, int32_t g, skml_sparse_group* info,
                            int32_t* table_host, uint64_t* flag_words_host, uint64_t* delta_words_host) {
-    if (!c || !s || !info || g < 0 || g >= s->g.G) return sfail(SKML_E_ARG, "bad group query");
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    if (!c || !s || !info || g < 0 || g >= s->g.G) return fail(SKML_E_ARG, "bad group query");
+    HIP_TRY(hipSetDevice(c->device));
     const SpGroups& G = s->g;
     std::memset(info, 0, sizeof(*info));
     info->size = (int32_t)(G.gstart[g + 1] - G.gstart[g]);
@@ -1034,7 +1015,7 @@ int skml_sparse_group_info(skml_ctx* c, const skml_sparse* s, int32_t g, skml_sp
 // code stream (cached in the payload).
 static int build_huffman(skml_ctx* c, skml_sparse* s) {
     if (s->huff_done) return SKML_OK;
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     const SpGroups& G = s->g;
     const int B = G.bin_num;
     const size_t nsym = (size_t)B + 1;
@@ -1047,9 +1028,9 @@ static int build_huffman(skml_ctx* c, skml_sparse* s) {
             if (G.gstart[g + 1] > G.gstart[g]) max_cells = std::max<int64_t>(max_cells, (int64_t)G.rows * G.cols[g]);
         uint32_t* hist = scratch<uint32_t>(c, kSlotDelta, (size_t)G.G * nsym);
         uint64_t* lut = scratch<uint64_t>(c, kSlotCells, (size_t)G.G * nsym);
-        if (!hist || !lut) return sfail(SKML_E_OOM, "huffman scratch");
-        SP_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)G.G * nsym, st));
-        SP_HIP(launch_huff_hist(st, s->tables, s->g_dev, G.G, B, max_cells, hist));
+        if (!hist || !lut) return fail(SKML_E_OOM, "huffman scratch");
+        HIP_TRY(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)G.G * nsym, st));
+        HIP_TRY(launch_huff_hist(st, s->tables, s->g_dev, G.G, B, max_cells, hist));
         std::vector<uint32_t> hh((size_t)G.G * nsym);
         if (int e = sync_to_host(c, hh.data(), hist, sizeof(uint32_t) * hh.size())) return e;
         std::vector<uint64_t> lh((size_t)G.G * nsym, 0);
@@ -1065,7 +1046,7 @@ static int build_huffman(skml_ctx* c, skml_sparse* s) {
                 if (h[v]) syms.emplace_back(v, h[v]);
             if (G.fill >= 0 && h[B]) syms.emplace_back(G.fill, h[B]);
             if (!hb.build(syms, s->huff_items[(size_t)g]))
-                return sfail(SKML_E_STATE, "Huffman code longer than 32 bits (group %d)", g);
+                return fail(SKML_E_STATE, "Huffman code longer than 32 bits (group %d)", g);
             for (const HuffItem& it : s->huff_items[(size_t)g]) {
                 const int sym = (it.value >= 0 && it.value < B) ? it.value : B;
                 lh[(size_t)g * nsym + sym] = ((uint64_t)it.nbits << 32) | (uint32_t)it.bits;
@@ -1074,20 +1055,20 @@ static int build_huffman(skml_ctx* c, skml_sparse* s) {
             bit += s->huff_bits[(size_t)g];
         }
         s->huff_bit0[(size_t)G.G] = bit;
-        SP_HIP(hipMemcpyAsync(lut, lh.data(), sizeof(uint64_t) * lh.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(lut, lh.data(), sizeof(uint64_t) * lh.size(), hipMemcpyHostToDevice, st));
         const int64_t tiles = sp_tiles(s->ncells, kSpTile);
         uint64_t* ts = scratch<uint64_t>(c, kSlotTiles, (size_t)tiles + 1);
         int64_t* gbit = scratch<int64_t>(c, kSlotSmall, kMaxGroups + 1);
-        if (!ts || !gbit) return sfail(SKML_E_OOM, "huffman scratch");
-        SP_HIP(launch_huff_lens(st, s->tables, s->ncells, s->g_dev, B, lut, ts));
+        if (!ts || !gbit) return fail(SKML_E_OOM, "huffman scratch");
+        HIP_TRY(launch_huff_lens(st, s->tables, s->ncells, s->g_dev, B, lut, ts));
         uint64_t total = 0;
         if (int e = scan_tiles(c, ts, tiles, 1, &total)) return e;
-        if ((int64_t)total != bit) return sfail(SKML_E_STATE, "huffman bit count mismatch");
+        if ((int64_t)total != bit) return fail(SKML_E_STATE, "huffman bit count mismatch");
         s->n_huff_words = (bit + 63) / 64 + 1;
-        SP_HIP(hipMalloc(&s->huff_words, sizeof(uint64_t) * (size_t)s->n_huff_words));
-        SP_HIP(hipMemsetAsync(s->huff_words, 0, sizeof(uint64_t) * (size_t)s->n_huff_words, st));
-        SP_HIP(launch_huff_write(st, s->tables, s->ncells, s->g_dev, B, lut, ts, s->huff_words, gbit));
-        SP_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMalloc(&s->huff_words, sizeof(uint64_t) * (size_t)s->n_huff_words));
+        HIP_TRY(hipMemsetAsync(s->huff_words, 0, sizeof(uint64_t) * (size_t)s->n_huff_words, st));
+        HIP_TRY(launch_huff_write(st, s->tables, s->ncells, s->g_dev, B, lut, ts, s->huff_words, gbit));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     s->huff_done = true;
     return SKML_OK;
@@ -1131,7 +1112,7 @@ struct WireBuilder {
 // the trims of every long array (one small read-back), the layout on the host, then two kernels.
 int build_wire(skml_ctx* c, skml_sparse* s) {
     if (int e = build_huffman(c, s)) return e;
-    hipStream_t st = ctx_stream(c);
+    hipStream_t st = c->stream;
     const SpGroups& G = s->g;
     static const int32_t kBkdrSeed[8] = {0, 0, 0, 31, 131, 267, 1313, 13131};
     // the long arrays in stream order: every present sketch's Huffman words, then every present
@@ -1155,17 +1136,17 @@ int build_wire(skml_ctx* c, skml_sparse* s) {
     const size_t o_npre = o_nz + align_up(sizeof(uint64_t) * (size_t)std::max(nsec, 1), 256);
     const size_t meta_bytes = o_npre + sizeof(int64_t) * ((size_t)nsec + 1);
     uint8_t* meta = scratch<uint8_t>(c, kSlotWireMeta, meta_bytes);
-    if (!meta) return sfail(SKML_E_OOM, "wire scratch");
+    if (!meta) return fail(SKML_E_OOM, "wire scratch");
     WireSec* d_secs = reinterpret_cast<WireSec*>(meta);
     int64_t* d_pre = reinterpret_cast<int64_t*>(meta + o_pre);
     uint64_t* d_nz = reinterpret_cast<uint64_t*>(meta + o_nz);
     int64_t* d_npre = reinterpret_cast<int64_t*>(meta + o_npre);
     std::vector<uint64_t> nz((size_t)nsec, 0);
     if (nsec > 0) {
-        SP_HIP(hipMemcpyAsync(d_secs, secs.data(), sizeof(WireSec) * (size_t)nsec, hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(d_pre, wpre.data(), sizeof(int64_t) * wpre.size(), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemsetAsync(d_nz, 0, sizeof(uint64_t) * (size_t)nsec, st));
-        SP_HIP(launch_wire_lastnz(st, src, d_secs, nsec, d_nz));
+        HIP_TRY(hipMemcpyAsync(d_secs, secs.data(), sizeof(WireSec) * (size_t)nsec, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_pre, wpre.data(), sizeof(int64_t) * wpre.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_nz, 0, sizeof(uint64_t) * (size_t)nsec, st));
+        HIP_TRY(launch_wire_lastnz(st, src, d_secs, nsec, d_nz));
         if (int e = sync_to_host(c, nz.data(), d_nz, sizeof(uint64_t) * (size_t)nsec)) return e;
     }
     // the layout (GroupedMinMaxSketch.writeObject field order, see skml_sparse_serialize)
@@ -1220,13 +1201,13 @@ int build_wire(skml_ctx* c, skml_sparse* s) {
     for (int q = 0; q < nsec; q++) npre[(size_t)q + 1] = npre[(size_t)q] + secs[(size_t)q].nwords;
     // the stream: the small fields' pieces, then the long arrays
     void* wire = nullptr;
-    SP_HIP(hipMalloc(&wire, (size_t)std::max<int64_t>(w.total, 1)));
+    HIP_TRY(hipMalloc(&wire, (size_t)std::max<int64_t>(w.total, 1)));
     const int npieces = (int)(w.pieces.size() / 3);
     const size_t o_pcs = align_up(w.small.size(), 256);
     uint8_t* sm = scratch<uint8_t>(c, kSlotSmall, o_pcs + sizeof(int64_t) * w.pieces.size() + 8);
     if (!sm) {
         (void)hipFree(wire);
-        return sfail(SKML_E_OOM, "wire scratch");
+        return fail(SKML_E_OOM, "wire scratch");
     }
     auto fail_free = [&](int e) {
         (void)hipStreamSynchronize(st);
@@ -1236,7 +1217,7 @@ int build_wire(skml_ctx* c, skml_sparse* s) {
 #define W_HIP(expr)                                                                                         \
     do {                                                                                                    \
         hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail_free(sfail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
+        if (e_ != hipSuccess) return fail_free(fail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
     } while (0)
     if (!w.small.empty()) W_HIP(hipMemcpyAsync(sm, w.small.data(), w.small.size(), hipMemcpyHostToDevice, st));
     if (npieces > 0)
@@ -1262,16 +1243,16 @@ int build_wire(skml_ctx* c, skml_sparse* s) {
 // Int2IntHash object is (int HashFactory index, int size, int BKDR seed or 0).  Assembled on the
 // device (skml_wire.hip) and copied out once.
 int skml_sparse_serialize(skml_ctx* c, const skml_sparse* cs, uint8_t* buf, size_t cap, size_t* written) {
-    if (!c || !cs) return sfail(SKML_E_ARG, "bad serialise arguments");
-    SP_HIP(hipSetDevice(ctx_device(c)));
+    if (!c || !cs) return fail(SKML_E_ARG, "bad serialise arguments");
+    HIP_TRY(hipSetDevice(c->device));
     skml_sparse* s = const_cast<skml_sparse*>(cs);  // the Huffman streams and the wire are lazily built caches
     if (!s->wire_dev)
         if (int e = build_wire(c, s)) return e;
     if (written) *written = s->wire_bytes;
     if (!buf) return SKML_OK;
-    if (cap < s->wire_bytes) return sfail(SKML_E_ARG, "buffer capacity %zu < %zu", cap, s->wire_bytes);
-    SP_HIP(hipMemcpyAsync(buf, s->wire_dev, s->wire_bytes, hipMemcpyDeviceToHost, ctx_stream(c)));
-    SP_HIP(hipStreamSynchronize(ctx_stream(c)));
+    if (cap < s->wire_bytes) return fail(SKML_E_ARG, "buffer capacity %zu < %zu", cap, s->wire_bytes);
+    HIP_TRY(hipMemcpyAsync(buf, s->wire_dev, s->wire_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SKML_OK;
 }
 
@@ -1332,23 +1313,23 @@ int huff_tables(const std::vector<HuffItem>& items, int node_base, std::vector<i
     std::vector<int> prefix_node(kHuffLutSize, -1);  // subtree root of a long-code prefix
     std::vector<N> t;
     for (const HuffItem& it : items) {
-        if (it.nbits <= 0 || it.nbits > 31) return sfail(SKML_E_ARG, "Huffman code of %d bits", it.nbits);
+        if (it.nbits <= 0 || it.nbits > 31) return fail(SKML_E_ARG, "Huffman code of %d bits", it.nbits);
         const uint32_t code = (uint32_t)it.bits;
         if (it.nbits <= kHuffLutBits) {
             const uint32_t lo = code << (kHuffLutBits - it.nbits), hi = (code + 1) << (kHuffLutBits - it.nbits);
-            if (hi > (uint32_t)kHuffLutSize) return sfail(SKML_E_ARG, "Huffman code wider than its length");
+            if (hi > (uint32_t)kHuffLutSize) return fail(SKML_E_ARG, "Huffman code wider than its length");
             for (uint32_t k = lo; k < hi; k++) {
-                if (set[k]) return sfail(SKML_E_ARG, "Huffman codes are not prefix-free");
+                if (set[k]) return fail(SKML_E_ARG, "Huffman codes are not prefix-free");
                 set[k] = 1;
                 lut[l0 + k] = int2{it.value, it.nbits};
             }
             continue;
         }
         const uint32_t pre = code >> (it.nbits - kHuffLutBits);
-        if (pre >= (uint32_t)kHuffLutSize) return sfail(SKML_E_ARG, "Huffman code wider than its length");
+        if (pre >= (uint32_t)kHuffLutSize) return fail(SKML_E_ARG, "Huffman code wider than its length");
         int node = prefix_node[pre];
         if (node < 0) {
-            if (set[pre]) return sfail(SKML_E_ARG, "Huffman codes are not prefix-free");
+            if (set[pre]) return fail(SKML_E_ARG, "Huffman codes are not prefix-free");
             node = (int)t.size();
             t.push_back(N());
             prefix_node[pre] = node;
@@ -1356,7 +1337,7 @@ int huff_tables(const std::vector<HuffItem>& items, int node_base, std::vector<i
             lut[l0 + pre] = int2{node_base + node, -1};
         }
         for (int b = it.nbits - kHuffLutBits - 1; b >= 0; b--) {
-            if (t[(size_t)node].leaf) return sfail(SKML_E_ARG, "Huffman codes are not prefix-free");
+            if (t[(size_t)node].leaf) return fail(SKML_E_ARG, "Huffman codes are not prefix-free");
             const bool one = (code >> b) & 1u;
             int child = one ? t[(size_t)node].right : t[(size_t)node].left;
             if (child < 0) {
@@ -1368,17 +1349,17 @@ int huff_tables(const std::vector<HuffItem>& items, int node_base, std::vector<i
             node = child;
         }
         N& leaf = t[(size_t)node];
-        if (leaf.leaf || leaf.left >= 0 || leaf.right >= 0) return sfail(SKML_E_ARG, "Huffman codes are not prefix-free");
+        if (leaf.leaf || leaf.left >= 0 || leaf.right >= 0) return fail(SKML_E_ARG, "Huffman codes are not prefix-free");
         leaf.leaf = true;
         leaf.value = it.value;
     }
     for (int k = 0; k < kHuffLutSize; k++)
-        if (!set[k]) return sfail(SKML_E_ARG, "Huffman tree is not full");
+        if (!set[k]) return fail(SKML_E_ARG, "Huffman tree is not full");
     for (const N& nd : t) {
         if (nd.leaf) {
             nodes.push_back(int4{-1, -1, nd.value, 0});
         } else {
-            if (nd.left < 0 || nd.right < 0) return sfail(SKML_E_ARG, "Huffman tree is not full");
+            if (nd.left < 0 || nd.right < 0) return fail(SKML_E_ARG, "Huffman tree is not full");
             nodes.push_back(int4{node_base + nd.left, node_base + nd.right, 0, 0});
         }
     }
@@ -1393,13 +1374,13 @@ int huff_tables(const std::vector<HuffItem>& items, int node_base, std::vector<i
 int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const double* qvalues, int32_t nvalues,
                             skml_sparse** out) {
     if (!c || !buf || !out || nvalues < 0 || (nvalues > 0 && !qvalues))
-        return sfail(SKML_E_ARG, "bad deserialise arguments");
+        return fail(SKML_E_ARG, "bad deserialise arguments");
     *out = nullptr;
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     BeReader r{buf, len};
     skml_sparse* s = new skml_sparse();
-    s->device = ctx_device(c);
+    s->device = c->device;
     auto bail = [&](int e) {
         sparse_release(s);
         return e;
@@ -1411,8 +1392,8 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
     G.bin_num = r.i32();
     G.zero = r.i32();
     if (r.bad || G.G < 1 || G.G > kMaxGroups || G.rows < 0 || G.rows > kMaxRows || G.bin_num < 1)
-        return bail(sfail(SKML_E_ARG, "malformed GroupedMinMaxSketch stream (groups %d rows %d bins %d)", G.G, G.rows,
-                          G.bin_num));
+        return bail(fail(SKML_E_ARG, "malformed GroupedMinMaxSketch stream (groups %d rows %d bins %d)", G.G, G.rows,
+                         G.bin_num));
     s->params.group_num = G.G;
     s->params.row_num = G.rows;
     s->params.bin_num = G.bin_num;
@@ -1424,17 +1405,17 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         present[(size_t)g] = (char)r.byte();
         if (!present[(size_t)g]) continue;
         const int32_t rows = r.i32(), cols = r.i32(), zero = r.i32();
-        if (rows != G.rows || cols < 0 || zero != G.zero) return bail(sfail(SKML_E_ARG, "malformed MinMaxSketch %d", g));
+        if (rows != G.rows || cols < 0 || zero != G.zero) return bail(fail(SKML_E_ARG, "malformed MinMaxSketch %d", g));
         G.cols[g] = cols;
         for (int k = 0; k < rows; k++) {
             G.hash_ids[g][k] = r.i32();
             (void)r.i32();  // hash size (= cols)
             (void)r.i32();  // BKDR seed (a function of the hash id)
-            if (G.hash_ids[g][k] < 0 || G.hash_ids[g][k] > 7) return bail(sfail(SKML_E_ARG, "bad hash id"));
+            if (G.hash_ids[g][k] < 0 || G.hash_ids[g][k] > 7) return bail(fail(SKML_E_ARG, "bad hash id"));
         }
         HuffGroupIn& h = hg[(size_t)g];
         const int32_t ni = r.i32();
-        if (ni < 0 || (size_t)ni * 12 > len) return bail(sfail(SKML_E_ARG, "malformed Huffman items"));
+        if (ni < 0 || (size_t)ni * 12 > len) return bail(fail(SKML_E_ARG, "malformed Huffman items"));
         h.items.resize((size_t)ni);
         for (auto& it : h.items) {
             it.value = r.i32();
@@ -1442,10 +1423,10 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
             it.nbits = r.i32();
         }
         const int32_t nl = r.i32();
-        if (nl < 0 || !r.skip_longs((size_t)nl, &h.pos)) return bail(sfail(SKML_E_ARG, "malformed Huffman bit set"));
+        if (nl < 0 || !r.skip_longs((size_t)nl, &h.pos)) return bail(fail(SKML_E_ARG, "malformed Huffman bit set"));
         h.nlongs = nl;
         h.size = r.i32();
-        if (h.size != (int64_t)rows * cols) return bail(sfail(SKML_E_ARG, "Huffman size %lld != rows*cols", (long long)h.size));
+        if (h.size != (int64_t)rows * cols) return bail(fail(SKML_E_ARG, "Huffman size %lld != rows*cols", (long long)h.size));
         G.tab_off[g] = cells;
         cells += h.size;
     }
@@ -1465,7 +1446,7 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         G.gstart[g] = n;
         G.kind1_before[g] = k1;
         const int pres = r.byte();
-        if (pres != present[(size_t)g]) return bail(sfail(SKML_E_ARG, "sketch / encoder presence mismatch in group %d", g));
+        if (pres != present[(size_t)g]) return bail(fail(SKML_E_ARG, "sketch / encoder presence mismatch in group %d", g));
         if (!pres) {
             G.m[g] = 1;
             G.kind[g] = 0;
@@ -1477,11 +1458,11 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         G.m[g] = m;
         G.kind[g] = r.byte() ? 1 : 0;
         if (e.size < 0 || (m != 1 && m != 2 && m != 4 && m != 8 && m != 16))
-            return bail(sfail(SKML_E_ARG, "malformed DeltaAdaptiveEncoder %d (numIntervals %d)", g, m));
+            return bail(fail(SKML_E_ARG, "malformed DeltaAdaptiveEncoder %d (numIntervals %d)", g, m));
         const int32_t nfl = r.i32();
-        if (nfl < 0 || !r.skip_longs((size_t)nfl, &e.fpos)) return bail(sfail(SKML_E_ARG, "malformed BitSet"));
+        if (nfl < 0 || !r.skip_longs((size_t)nfl, &e.fpos)) return bail(fail(SKML_E_ARG, "malformed BitSet"));
         const int32_t ndl = r.i32();
-        if (ndl < 0 || !r.skip_longs((size_t)ndl, &e.dpos)) return bail(sfail(SKML_E_ARG, "malformed BitSet"));
+        if (ndl < 0 || !r.skip_longs((size_t)ndl, &e.dpos)) return bail(fail(SKML_E_ARG, "malformed BitSet"));
         e.fn = nfl;
         e.dn = ndl;
         e.bpi = 32 / m;
@@ -1490,12 +1471,12 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         n += e.size;
     }
     G.gstart[G.G] = n;
-    if (r.bad) return bail(sfail(SKML_E_ARG, "truncated GroupedMinMaxSketch stream"));
+    if (r.bad) return bail(fail(SKML_E_ARG, "truncated GroupedMinMaxSketch stream"));
     // the stream on the device, once
     // 16 bytes of slack: be64_at reads the aligned word after an unaligned long
     uint8_t* dstream = scratch<uint8_t>(c, kSlotWire, std::max<size_t>(len + 16, 64));
-    if (!dstream) return bail(sfail(SKML_E_OOM, "device copy of the stream"));
-    SP_HIP(hipMemcpyAsync(dstream, buf, len, hipMemcpyHostToDevice, st));
+    if (!dstream) return bail(fail(SKML_E_OOM, "device copy of the stream"));
+    HIP_TRY(hipMemcpyAsync(dstream, buf, len, hipMemcpyHostToDevice, st));
     // the flags' lengths: field sums of the fixed groups, zero selects of the unary ones
     std::vector<RdFlagSec> fx, un;
     std::vector<int> fx_g, un_g;
@@ -1521,21 +1502,21 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
     const size_t o_res = o_unp + align_up(sizeof(int64_t) * (nun + 1), 256);  // sums[nfx] | flen[nun]
     const size_t o_tz = o_res + align_up(sizeof(int64_t) * (nfx + nun + 1), 256);
     uint8_t* meta = scratch<uint8_t>(c, kSlotWireMeta, o_tz + sizeof(uint32_t) * (size_t)std::max<int64_t>(un_pre.back(), 1));
-    if (!meta) return bail(sfail(SKML_E_OOM, "readObject scratch"));
+    if (!meta) return bail(fail(SKML_E_OOM, "readObject scratch"));
     int64_t* d_res = reinterpret_cast<int64_t*>(meta + o_res);
     std::vector<int64_t> res(nfx + nun, 0);
     if (nfx + nun > 0) {
-        if (nfx) SP_HIP(hipMemcpyAsync(meta, fx.data(), sizeof(RdFlagSec) * nfx, hipMemcpyHostToDevice, st));
-        if (nun) SP_HIP(hipMemcpyAsync(meta + o_un, un.data(), sizeof(RdFlagSec) * nun, hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(meta + o_fxp, fx_pre.data(), sizeof(int64_t) * fx_pre.size(), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(meta + o_unp, un_pre.data(), sizeof(int64_t) * un_pre.size(), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemsetAsync(d_res, 0, sizeof(int64_t) * (nfx + nun), st));
-        SP_HIP(launch_rd_fixed_sum(st, dstream, reinterpret_cast<const RdFlagSec*>(meta),
-                                   reinterpret_cast<const int64_t*>(meta + o_fxp), (int)nfx, fx_pre.back(),
-                                   reinterpret_cast<uint64_t*>(d_res)));
-        SP_HIP(launch_rd_unary(st, dstream, reinterpret_cast<const RdFlagSec*>(meta + o_un),
-                               reinterpret_cast<const int64_t*>(meta + o_unp), (int)nun, un_pre.back(),
-                               reinterpret_cast<uint32_t*>(meta + o_tz), d_res + nfx));
+        if (nfx) HIP_TRY(hipMemcpyAsync(meta, fx.data(), sizeof(RdFlagSec) * nfx, hipMemcpyHostToDevice, st));
+        if (nun) HIP_TRY(hipMemcpyAsync(meta + o_un, un.data(), sizeof(RdFlagSec) * nun, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(meta + o_fxp, fx_pre.data(), sizeof(int64_t) * fx_pre.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(meta + o_unp, un_pre.data(), sizeof(int64_t) * un_pre.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_res, 0, sizeof(int64_t) * (nfx + nun), st));
+        HIP_TRY(launch_rd_fixed_sum(st, dstream, reinterpret_cast<const RdFlagSec*>(meta),
+                                    reinterpret_cast<const int64_t*>(meta + o_fxp), (int)nfx, fx_pre.back(),
+                                    reinterpret_cast<uint64_t*>(d_res)));
+        HIP_TRY(launch_rd_unary(st, dstream, reinterpret_cast<const RdFlagSec*>(meta + o_un),
+                                reinterpret_cast<const int64_t*>(meta + o_unp), (int)nun, un_pre.back(),
+                                reinterpret_cast<uint32_t*>(meta + o_tz), d_res + nfx));
         if (int e = sync_to_host(c, res.data(), d_res, sizeof(int64_t) * res.size())) return bail(e);
     }
     std::vector<int64_t> flen((size_t)G.G, 0), dlen((size_t)G.G, 0);
@@ -1547,7 +1528,7 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
     for (size_t q = 0; q < nun; q++) {
         const int g = un_g[q];
         flen[(size_t)g] = res[nfx + q];
-        if (flen[(size_t)g] < enc[(size_t)g].size) return bail(sfail(SKML_E_ARG, "unary flags of group %d do not end", g));
+        if (flen[(size_t)g] < enc[(size_t)g].size) return bail(fail(SKML_E_ARG, "unary flags of group %d do not end", g));
         dlen[(size_t)g] = (int64_t)enc[(size_t)g].bpi * (flen[(size_t)g] - enc[(size_t)g].size);
     }
     int64_t fbits = 0, dbits = 0;
@@ -1561,7 +1542,7 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
             dlen[(size_t)g] = (int64_t)e.bpi * e.size;
         }
         if (e.fn > (flen[(size_t)g] + 63) / 64 || e.dn > (dlen[(size_t)g] + 63) / 64)
-            return bail(sfail(SKML_E_ARG, "DeltaAdaptiveEncoder %d holds bits past its stream", g));
+            return bail(fail(SKML_E_ARG, "DeltaAdaptiveEncoder %d holds bits past its stream", g));
         fbits += flen[(size_t)g];
         dbits += dlen[(size_t)g];
     }
@@ -1587,7 +1568,7 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         hipMalloc(&s->flag_words, sizeof(uint64_t) * (size_t)s->n_flag_words) != hipSuccess ||
         hipMalloc(&s->delta_words, sizeof(uint64_t) * (size_t)s->n_delta_words) != hipSuccess ||
         hipMalloc(&s->tables, sizeof(int32_t) * (size_t)std::max<int64_t>(cells, 1)) != hipSuccess)
-        return bail(sfail(SKML_E_OOM, "deserialised payload"));
+        return bail(fail(SKML_E_OOM, "deserialised payload"));
     {
         std::vector<RdBitSec> fsec((size_t)G.G), dsec((size_t)G.G);
         for (int g = 0; g < G.G; g++) {
@@ -1597,16 +1578,16 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         const size_t o_d = align_up(sizeof(RdBitSec) * (size_t)G.G, 256);
         const size_t o_fo = 2 * o_d, o_do = o_fo + align_up(sizeof(int64_t) * (size_t)(G.G + 1), 256);
         uint8_t* m2 = scratch<uint8_t>(c, kSlotStatus, o_do + sizeof(int64_t) * (size_t)(G.G + 1));
-        if (!m2) return bail(sfail(SKML_E_OOM, "readObject scratch"));
-        SP_HIP(hipMemcpyAsync(m2, fsec.data(), sizeof(RdBitSec) * fsec.size(), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(m2 + o_d, dsec.data(), sizeof(RdBitSec) * dsec.size(), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(m2 + o_fo, G.fb, sizeof(int64_t) * (size_t)(G.G + 1), hipMemcpyHostToDevice, st));
-        SP_HIP(hipMemcpyAsync(m2 + o_do, G.db, sizeof(int64_t) * (size_t)(G.G + 1), hipMemcpyHostToDevice, st));
-        SP_HIP(launch_rd_stream(st, dstream, reinterpret_cast<const RdBitSec*>(m2),
-                                reinterpret_cast<const int64_t*>(m2 + o_fo), G.G, s->n_flag_words, s->flag_words));
-        SP_HIP(launch_rd_stream(st, dstream, reinterpret_cast<const RdBitSec*>(m2 + o_d),
-                                reinterpret_cast<const int64_t*>(m2 + o_do), G.G, s->n_delta_words, s->delta_words));
-        SP_HIP(hipStreamSynchronize(st));  // the host tables above are the copies' sources
+        if (!m2) return bail(fail(SKML_E_OOM, "readObject scratch"));
+        HIP_TRY(hipMemcpyAsync(m2, fsec.data(), sizeof(RdBitSec) * fsec.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m2 + o_d, dsec.data(), sizeof(RdBitSec) * dsec.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m2 + o_fo, G.fb, sizeof(int64_t) * (size_t)(G.G + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m2 + o_do, G.db, sizeof(int64_t) * (size_t)(G.G + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_rd_stream(st, dstream, reinterpret_cast<const RdBitSec*>(m2),
+                                 reinterpret_cast<const int64_t*>(m2 + o_fo), G.G, s->n_flag_words, s->flag_words));
+        HIP_TRY(launch_rd_stream(st, dstream, reinterpret_cast<const RdBitSec*>(m2 + o_d),
+                                 reinterpret_cast<const int64_t*>(m2 + o_do), G.G, s->n_delta_words, s->delta_words));
+        HIP_TRY(hipStreamSynchronize(st));  // the host tables above are the copies' sources
     }
     if (int e = upload_groups(c, s)) return bail(e);
     // HuffmanEncoder.decode of every group's table
@@ -1619,9 +1600,9 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
     for (int g = 0; g < G.G; g++) {
         const HuffGroupIn& h = hg[(size_t)g];
         if (!present[(size_t)g] || h.size == 0) continue;
-        if (h.items.empty()) return bail(sfail(SKML_E_ARG, "Huffman items missing in group %d", g));
+        if (h.items.empty()) return bail(fail(SKML_E_ARG, "Huffman items missing in group %d", g));
         if (h.items.size() == 1) {  // a one-symbol tree: zero-bit codes
-            SP_HIP(launch_fill_i32(st, s->tables + G.tab_off[g], h.size, h.items[0].value));
+            HIP_TRY(launch_fill_i32(st, s->tables + G.tab_off[g], h.size, h.items[0].value));
             continue;
         }
         HuffDecGroup d;
@@ -1665,7 +1646,7 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         const size_t b_wp = align_up(sizeof(int64_t) * (wpos.size() + wpre.size()), 256);
         const size_t total = b_grp + b_seg + 3 * b_i64 + b_cnt + 256 + b_lut + b_nod + b_wrd + b_wp;
         char* blk = nullptr;
-        SP_HIP(hipMalloc(&blk, total));
+        HIP_TRY(hipMalloc(&blk, total));
         auto run = [&]() -> int {
             char* q = blk;
             auto* d_grp = (HuffDecGroup*)q; q += b_grp;
@@ -1679,34 +1660,34 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
             auto* d_nod = (int4*)q; q += b_nod;
             auto* d_wrd = (uint64_t*)q; q += b_wrd;
             auto* d_wp = (int64_t*)q;
-            SP_HIP(hipMemcpyAsync(d_wp, wpos.data(), sizeof(int64_t) * wpos.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemcpyAsync(d_wp + wpos.size(), wpre.data(), sizeof(int64_t) * wpre.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemsetAsync(d_wrd + wpre.back(), 0, sizeof(uint64_t), st));
-            SP_HIP(launch_rd_words(st, dstream, d_wp, d_wp + wpos.size(), (int)wpos.size(), wpre.back(), d_wrd));
-            SP_HIP(hipMemcpyAsync(d_grp, dg.data(), sizeof(HuffDecGroup) * dg.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemcpyAsync(d_seg, segs.data(), sizeof(HuffSeg) * segs.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemcpyAsync(d_start, starts.data(), sizeof(int64_t) * starts.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemcpyAsync(d_lut, lut.data(), sizeof(int2) * lut.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemcpyAsync(d_nod, nodes.data(), sizeof(int4) * nodes.size(), hipMemcpyHostToDevice, st));
-            SP_HIP(hipMemsetAsync(d_cnt, 0, b_cnt, st));
-            SP_HIP(launch_huff_spec(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_ea, d_cnt));
+            HIP_TRY(hipMemcpyAsync(d_wp, wpos.data(), sizeof(int64_t) * wpos.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_wp + wpos.size(), wpre.data(), sizeof(int64_t) * wpre.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_wrd + wpre.back(), 0, sizeof(uint64_t), st));
+            HIP_TRY(launch_rd_words(st, dstream, d_wp, d_wp + wpos.size(), (int)wpos.size(), wpre.back(), d_wrd));
+            HIP_TRY(hipMemcpyAsync(d_grp, dg.data(), sizeof(HuffDecGroup) * dg.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_seg, segs.data(), sizeof(HuffSeg) * segs.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_start, starts.data(), sizeof(int64_t) * starts.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_lut, lut.data(), sizeof(int2) * lut.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_nod, nodes.data(), sizeof(int4) * nodes.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, b_cnt, st));
+            HIP_TRY(launch_huff_spec(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_ea, d_cnt));
             // resynchronise until every segment starts where its predecessor ends
             for (int round = 0;; round++) {
-                if (round > ns + 1) return sfail(SKML_E_ARG, "Huffman stream does not resynchronise");
-                SP_HIP(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-                SP_HIP(launch_huff_sync(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_ea, d_eb, d_cnt, d_flag));
+                if (round > ns + 1) return fail(SKML_E_ARG, "Huffman stream does not resynchronise");
+                HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+                HIP_TRY(launch_huff_sync(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_ea, d_eb, d_cnt, d_flag));
                 unsigned changed = 0;
                 if (int e = sync_to_host(c, &changed, d_flag, sizeof(unsigned))) return e;
                 std::swap(d_ea, d_eb);
                 if (!changed) break;
             }
-            SP_HIP(launch_scan_cols(st, d_cnt, ns, 1));  // exclusive scan: symbol offsets
-            SP_HIP(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-            SP_HIP(launch_huff_decode_write(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_cnt, s->tables,
-                                            d_flag));
+            HIP_TRY(launch_scan_cols(st, d_cnt, ns, 1));  // exclusive scan: symbol offsets
+            HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+            HIP_TRY(launch_huff_decode_write(st, ns, d_seg, d_grp, d_wrd, d_lut, d_nod, d_start, d_cnt, s->tables,
+                                             d_flag));
             unsigned err = 0;
             if (int e = sync_to_host(c, &err, d_flag, sizeof(unsigned))) return e;
-            if (err) return sfail(SKML_E_ARG, "Huffman stream holds a different number of symbols than size");
+            if (err) return fail(SKML_E_ARG, "Huffman stream holds a different number of symbols than size");
             return SKML_OK;
         };
         const int e = run();
@@ -1714,22 +1695,22 @@ int skml_sparse_deserialize(skml_ctx* c, const uint8_t* buf, size_t len, const d
         (void)hipFree(blk);
         if (e) return bail(e);
     }
-    SP_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     *out = s;
     return SKML_OK;
 }
 
 // GroupedMinMaxSketch.restore (GroupedMinMaxSketch.java:123-146) + Sort.merge: keys and int32 bins.
 int skml_sparse_restore_bins(skml_ctx* c, const skml_sparse* s, int32_t* keys_dev, int32_t* bins_dev) {
-    if (!c || !s) return sfail(SKML_E_ARG, "bad restore arguments");
+    if (!c || !s) return fail(SKML_E_ARG, "bad restore arguments");
     const int64_t n = s->nnz;
     if (n == 0) return SKML_OK;
-    if (!keys_dev || !bins_dev) return sfail(SKML_E_ARG, "keys/bins are NULL");
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+    if (!keys_dev || !bins_dev) return fail(SKML_E_ARG, "keys/bins are NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     int32_t* gk = scratch<int32_t>(c, kSlotGKeys, (size_t)n);
     int32_t* gb = scratch<int32_t>(c, kSlotGBins, (size_t)n);
-    if (!gk || !gb) return sfail(SKML_E_OOM, "restore scratch");
+    if (!gk || !gb) return fail(SKML_E_OOM, "restore scratch");
     RsMerge rm;
     if (int e = rs_merge_prepare(c, s, &rm)) return e;
     const RunBoundsOut rbo = rm.query_bounds();  // the merge's key-range bounds from the query
@@ -1738,12 +1719,12 @@ int skml_sparse_restore_bins(skml_ctx* c, const skml_sparse* s, int32_t* keys_de
     if (int e = rs_merge_start(c, s, rm, gk, gb, keys_dev, bins_dev, 0, nullptr, 0, &pending)) return e;
     if (!pending)
         if (int e = merge_groups(c, s, gk, gb, keys_dev, bins_dev)) return e;
-    SP_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     t_merge_path = s->g.G < 2 ? 0 : pending ? 1 : 2;
     if (pending && *pending) {  // not regular: the merge rounds decide
         t_merge_path = 3;
         if (int e = merge_groups(c, s, gk, gb, keys_dev, bins_dev)) return e;
-        SP_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return SKML_OK;
 }
@@ -1774,7 +1755,7 @@ BlobLayout blob_layout(const skml_sparse* s) {
 // A blob's group table, checked for the invariants the decode kernels index by (a corrupt or
 // foreign blob must fail here, not fault on the device).
 int check_blob_groups(const SpBlobHeader& h, const SpGroups& G) {
-    auto bad = [](const char* what) { return sfail(SKML_E_ARG, "sparse blob: inconsistent %s", what); };
+    auto bad = [](const char* what) { return fail(SKML_E_ARG, "sparse blob: inconsistent %s", what); };
     if (G.G < 1 || G.G > kMaxGroups || G.rows < 0 || G.rows > kMaxRows) return bad("group / row count");
     if (G.bin_num < 1 || G.bin_num > h.nvalues || G.zero < 0 || G.zero >= G.bin_num) return bad("bins");
     if (h.version >= 2 && h.table_width != 32 && h.table_width != tnar_width_for(G.bin_num)) return bad("cell width");
@@ -1804,16 +1785,16 @@ int check_blob_groups(const SpBlobHeader& h, const SpGroups& G) {
 // A blob's header, checked against the `len` bytes it may span.
 int blob_table_width(const SpBlobHeader* h) { return h->version >= 2 ? h->table_width : 32; }
 int blob_check_header(const SpBlobHeader* h, size_t len) {
-    if (h->magic != kSpBlobMagic || h->version < 1 || h->version > 2) return sfail(SKML_E_STATE, "not a sparse blob");
+    if (h->magic != kSpBlobMagic || h->version < 1 || h->version > 2) return fail(SKML_E_STATE, "not a sparse blob");
     const int tw = blob_table_width(h);
-    if (tw != 8 && tw != 16 && tw != 32) return sfail(SKML_E_ARG, "sparse blob: cell width %d", tw);
+    if (tw != 8 && tw != 16 && tw != 32) return fail(SKML_E_ARG, "sparse blob: cell width %d", tw);
     if (h->total_bytes < 256 || (size_t)h->total_bytes > len || h->nnz < 0 || h->nnz > INT32_MAX || h->ncells < 0 ||
         h->nvalues < 1 || h->nvalues > SKML_MAX_BINS || h->quant_bytes < kHeaderBytes ||
         h->off_groups != 256 || h->off_quant < h->off_groups + (int64_t)sizeof(SpGroups) ||
         h->off_values < h->off_quant + h->quant_bytes || h->off_tables < h->off_values + 8 * (int64_t)h->nvalues ||
         h->off_flags < h->off_tables + tw / 8 * h->ncells || h->off_deltas < h->off_flags + 8 * h->n_flag_words ||
         h->total_bytes < h->off_deltas + 8 * h->n_delta_words || (h->off_tables | h->off_flags | h->off_deltas) & 255)
-        return sfail(SKML_E_ARG, "sparse blob: inconsistent section offsets");
+        return fail(SKML_E_ARG, "sparse blob: inconsistent section offsets");
     return SKML_OK;
 }
 
@@ -1828,7 +1809,7 @@ int blob_view(skml_ctx* c, const uint8_t* dev, const SpBlobHeader& h, const uint
     view->splits.assign(sp, sp + ns);
     const double* qv = reinterpret_cast<const double*>(meta + h.off_values);
     view->qvalues.assign(qv, qv + h.nvalues);
-    view->device = ctx_device(c);
+    view->device = c->device;
     view->nnz = h.nnz;
     view->params = h.params;
     view->ncells = h.ncells;
@@ -1853,29 +1834,29 @@ int blob_view(skml_ctx* c, const uint8_t* dev, const SpBlobHeader& h, const uint
 // per blob and section cost ~20 us of host round trip each, 16 of them for 8 payloads).
 int blob_metas(skml_ctx* c, const uint8_t* dev, int P, size_t stride, SpBlobHeader* hs, skml_sparse* views) {
     if (!dev || P < 1 || stride < 256 || (stride & 255) || (reinterpret_cast<uintptr_t>(dev) & 255))
-        return sfail(SKML_E_ARG, "sparse blob: NULL, shorter than its header or not 256-byte aligned");
-    hipStream_t st = ctx_stream(c);
+        return fail(SKML_E_ARG, "sparse blob: NULL, shorter than its header or not 256-byte aligned");
+    hipStream_t st = c->stream;
     size_t w = std::min<size_t>(stride, 16384);
     uint8_t* pin = static_cast<uint8_t*>(ctx_pinned(c, w * (size_t)P));
-    if (!pin) return sfail(SKML_E_OOM, "pinned staging of %zu bytes", w * (size_t)P);
-    SP_HIP(hipMemcpy2DAsync(pin, w, dev, stride, w, (size_t)P, hipMemcpyDeviceToHost, st));
-    SP_HIP(hipStreamSynchronize(st));
+    if (!pin) return fail(SKML_E_OOM, "pinned staging of %zu bytes", w * (size_t)P);
+    HIP_TRY(hipMemcpy2DAsync(pin, w, dev, stride, w, (size_t)P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     size_t meta_max = 0;
     for (int p = 0; p < P; p++) {
         std::memcpy(&hs[p], pin + (size_t)p * w, sizeof(SpBlobHeader));
-        if (int e = blob_check_header(&hs[p], stride)) return sfail(e, "payload %d: %s", p, skml_last_error());
+        if (int e = blob_check_header(&hs[p], stride)) return fail(e, "payload %d: %s", p, skml_last_error());
         meta_max = std::max(meta_max, (size_t)hs[p].off_tables);
     }
     if (meta_max > w) {  // off_tables is a multiple of 256 below total_bytes <= stride
         w = meta_max;
         pin = static_cast<uint8_t*>(ctx_pinned(c, w * (size_t)P));
-        if (!pin) return sfail(SKML_E_OOM, "pinned staging of %zu bytes", w * (size_t)P);
-        SP_HIP(hipMemcpy2DAsync(pin, w, dev, stride, w, (size_t)P, hipMemcpyDeviceToHost, st));
-        SP_HIP(hipStreamSynchronize(st));
+        if (!pin) return fail(SKML_E_OOM, "pinned staging of %zu bytes", w * (size_t)P);
+        HIP_TRY(hipMemcpy2DAsync(pin, w, dev, stride, w, (size_t)P, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     for (int p = 0; p < P; p++)
         if (int e = blob_view(c, dev + (size_t)p * stride, hs[p], pin + (size_t)p * w, &views[p]))
-            return sfail(e, "payload %d: %s", p, skml_last_error());
+            return fail(e, "payload %d: %s", p, skml_last_error());
     return SKML_OK;
 }
 
@@ -1883,7 +1864,7 @@ int blob_metas(skml_ctx* c, const uint8_t* dev, int P, size_t stride, SpBlobHead
 // non-owning skml_sparse view of its device sections.
 int blob_meta(skml_ctx* c, const uint8_t* dev, size_t len, SpBlobHeader* h, skml_sparse* view) {
     if (!dev || len < 256 || (reinterpret_cast<uintptr_t>(dev) & 255))
-        return sfail(SKML_E_ARG, "sparse blob: NULL, shorter than its header or not 256-byte aligned");
+        return fail(SKML_E_ARG, "sparse blob: NULL, shorter than its header or not 256-byte aligned");
     if (int e = sync_to_host(c, h, dev, sizeof(*h))) return e;
     if (int e = blob_check_header(h, len)) return e;
     std::vector<uint8_t> meta((size_t)h->off_tables);
@@ -1908,22 +1889,22 @@ struct ViewGuard {
 extern "C" {
 
 int skml_sparse_export_bytes(const skml_sparse* s, size_t* bytes) {
-    if (!s || !bytes) return sfail(SKML_E_ARG, "NULL argument");
+    if (!s || !bytes) return fail(SKML_E_ARG, "NULL argument");
     *bytes = blob_layout(s).total;
     return SKML_OK;
 }
 
 int skml_sparse_export(skml_ctx* c, const skml_sparse* s, void* dst, size_t cap) {
-    if (!c || !s || !dst || (reinterpret_cast<uintptr_t>(dst) & 255)) return sfail(SKML_E_ARG, "bad export arguments");
+    if (!c || !s || !dst || (reinterpret_cast<uintptr_t>(dst) & 255)) return fail(SKML_E_ARG, "bad export arguments");
     const BlobLayout L = blob_layout(s);
-    if (cap < L.total) return sfail(SKML_E_ARG, "export capacity %zu < %zu", cap, L.total);
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+    if (cap < L.total) return fail(SKML_E_ARG, "export capacity %zu < %zu", cap, L.total);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     // the host-side sections go through the context's pinned staging in one copy
     const size_t host_bytes = L.off_tables;
     uint8_t* pin = static_cast<uint8_t*>(ctx_pinned(c, host_bytes));
-    if (!pin) return sfail(SKML_E_OOM, "pinned staging");
-    SP_HIP(hipStreamSynchronize(st));  // the staging buffer may still feed an earlier copy
+    if (!pin) return fail(SKML_E_OOM, "pinned staging");
+    HIP_TRY(hipStreamSynchronize(st));  // the staging buffer may still feed an earlier copy
     std::memset(pin, 0, host_bytes);
     SpBlobHeader h{};
     h.magic = kSpBlobMagic;
@@ -1954,27 +1935,27 @@ int skml_sparse_export(skml_ctx* c, const skml_sparse* s, void* dst, size_t cap)
         std::memcpy(pin + L.off_quant + kHeaderBytes, s->splits.data(), sizeof(double) * s->splits.size());
     if (!s->qvalues.empty()) std::memcpy(pin + L.off_values, s->qvalues.data(), sizeof(double) * s->qvalues.size());
     uint8_t* d = static_cast<uint8_t*>(dst);
-    SP_HIP(hipMemcpyAsync(d, pin, host_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d, pin, host_bytes, hipMemcpyHostToDevice, st));
     if (s->ncells > 0)  // the exact narrow image when the payload has one, else the int32 cells
-        SP_HIP(hipMemcpyAsync(d + L.off_tables, s->tnar ? s->tnar : static_cast<const void*>(s->tables),
-                              (size_t)L.table_width / 8 * (size_t)s->ncells, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d + L.off_tables, s->tnar ? s->tnar : static_cast<const void*>(s->tables),
+                               (size_t)L.table_width / 8 * (size_t)s->ncells, hipMemcpyDeviceToDevice, st));
     if (s->n_flag_words > 0)
-        SP_HIP(hipMemcpyAsync(d + L.off_flags, s->flag_words, sizeof(uint64_t) * (size_t)s->n_flag_words,
-                              hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d + L.off_flags, s->flag_words, sizeof(uint64_t) * (size_t)s->n_flag_words,
+                               hipMemcpyDeviceToDevice, st));
     if (s->n_delta_words > 0)
-        SP_HIP(hipMemcpyAsync(d + L.off_deltas, s->delta_words, sizeof(uint64_t) * (size_t)s->n_delta_words,
-                              hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d + L.off_deltas, s->delta_words, sizeof(uint64_t) * (size_t)s->n_delta_words,
+                               hipMemcpyDeviceToDevice, st));
     // the copies read the payload's block: they complete before the call returns, so a payload
     // freed right after its export hands the pool a block with no pending reader (BlockPool)
-    SP_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SKML_OK;
 }
 
 int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** out) {
-    if (!c || !out) return sfail(SKML_E_ARG, "bad import arguments");
+    if (!c || !out) return fail(SKML_E_ARG, "bad import arguments");
     *out = nullptr;
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     SpBlobHeader h;
     skml_sparse view;
     ViewGuard vg{&view};
@@ -2005,7 +1986,7 @@ int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** 
     char* blk = static_cast<char*>(block_get(s->device, total, &s->block_cap));
     if (!blk) {
         sparse_release(s);
-        return sfail(SKML_E_OOM, "imported sparse payload of %zu bytes", total);
+        return fail(SKML_E_OOM, "imported sparse payload of %zu bytes", total);
     }
     s->qv_dev = reinterpret_cast<double*>(blk + o_qv);
     s->block = blk;
@@ -2023,7 +2004,7 @@ int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** 
 #define IMP_HIP(expr)                                                                                        \
     do {                                                                                                     \
         hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return fail_rel(sfail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
+        if (e_ != hipSuccess) return fail_rel(fail(SKML_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
     } while (0)
     IMP_HIP(hipMemcpyAsync(s->g_dev, view.g_dev, sizeof(SpGroups), hipMemcpyDeviceToDevice, st));
     if (!s->qvalues.empty())  // the blob's values section: the device copy of quantValues
@@ -2060,9 +2041,9 @@ int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** 
 int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
                                double* out) {
     if (!c || !blobs || P < 1 || dim < 0 || dim > (int64_t)INT32_MAX || (dim > 0 && !out) || stride % 256)
-        return sfail(SKML_E_ARG, "bad sparse decode_sum arguments (P >= 1, 256-byte stride, dim in Java int)");
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+        return fail(SKML_E_ARG, "bad sparse decode_sum arguments (P >= 1, 256-byte stride, dim in Java int)");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     std::vector<SpBlobHeader> hs((size_t)P);
     std::vector<skml_sparse> views((size_t)P);  // non-owning: skml_sparse frees nothing on destruction
     if (int e = blob_metas(c, static_cast<const uint8_t*>(blobs), P, stride, hs.data(), views.data())) return e;
@@ -2084,15 +2065,15 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
     // constructor reads indices.head (SparseDoubleGradient.scala:11) and throws: so does the sum
     for (int p = 0; p < P; p++)
         if (views[(size_t)p].nnz == 0)
-            return sfail(SKML_E_ARG, "payload %d restores no keys: head of empty list (SparseDoubleGradient.scala:11)", p);
+            return fail(SKML_E_ARG, "payload %d restores no keys: head of empty list (SparseDoubleGradient.scala:11)", p);
     std::vector<int> todo;
     for (int p = 0; p < P; p++) todo.push_back(p);
     uint8_t* small = scratch<uint8_t>(c, kSlotStatus, 1024 + sizeof(AggPayload) * (size_t)P);
-    if (!small) return sfail(SKML_E_OOM, "decode_sum scratch");
+    if (!small) return fail(SKML_E_OOM, "decode_sum scratch");
     unsigned* err = reinterpret_cast<unsigned*>(small);
     uint64_t* live = reinterpret_cast<uint64_t*>(small + 256);
     AggPayload* d_pays = reinterpret_cast<AggPayload*>(small + 1024);
-    SP_HIP(hipMemsetAsync(err, 0, sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(err, 0, sizeof(unsigned), st));
     size_t at = 0;
     bool first = true;
     while (at < todo.size()) {
@@ -2115,8 +2096,8 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
         int32_t* gk = scratch<int32_t>(c, kSlotCKeys, (size_t)nk);
         uint8_t* gbn = scratch<uint8_t>(c, kSlotCVals, (size_t)nbb);  // 1 or 2 bytes per bin
         int32_t* bounds = scratch<int32_t>(c, kSlotCells, (size_t)nb);
-        if (!gk || !gbn || !bounds) return sfail(SKML_E_OOM, "decode_sum scratch (%lld keys)", (long long)nk);
-        SP_HIP(hipMemsetAsync(bounds, 0, sizeof(int32_t) * (size_t)nb, st));  // empty groups: every bound 0
+        if (!gk || !gbn || !bounds) return fail(SKML_E_OOM, "decode_sum scratch (%lld keys)", (long long)nk);
+        HIP_TRY(hipMemsetAsync(bounds, 0, sizeof(int32_t) * (size_t)nb, st));  // empty groups: every bound 0
         // two lanes: payloads alternate between the caller's stream and the side context's (each
         // restore is a chain of small latency-bound kernels; two chains fill the chip better),
         // joined before the tiles; SKML_SERIAL, SKML_FORM_AGG_ONE_LANE or a single payload keep one
@@ -2124,9 +2105,9 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
         hipStream_t side_st = nullptr;
         hipEvent_t ev_fork = nullptr, ev_join = nullptr;
         if (end - at > 1 && form(SKML_FORM_AGG_ONE_LANE) != 1 && ctx_side_fork(c, &side_st, &ev_fork, &ev_join) == SKML_OK) {
-            lanes[1] = ctx_side_ctx(c);
-            SP_HIP(hipEventRecord(ev_fork, st));
-            SP_HIP(hipStreamWaitEvent(side_st, ev_fork, 0));
+            lanes[1] = c->side;
+            HIP_TRY(hipEventRecord(ev_fork, st));
+            HIP_TRY(hipStreamWaitEvent(side_st, ev_fork, 0));
         }
         std::vector<AggPayload> pays;
         int64_t ko = 0, bbo = 0, bo = 0;
@@ -2134,7 +2115,7 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
             const int p = todo[q];
             const int li = lanes[1] && ((q - at) & 1) ? 1 : 0;
             skml_ctx* lc = lanes[li];
-            hipStream_t ls = ctx_stream(lc);
+            hipStream_t ls = lc->stream;
             uint64_t* llive = live + li;
             const skml_sparse& v = views[(size_t)p];
             AggPayload a{};
@@ -2168,7 +2149,7 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
             if (int e = decode_groups(lc, &v, gk + ko, nullptr, true, &dv)) return join(e);
             if (v.nnz > lim) {  // live <= nnz: only then can toAuto pick the dense form
                 if (launch_count_live(ls, a.gb, a.bw, v.nnz, a.qv, llive) != hipSuccess)
-                    return join(sfail(SKML_E_HIP, "count_live launch failed"));
+                    return join(fail(SKML_E_HIP, "count_live launch failed"));
                 uint64_t nlive = 0;
                 if (int e = sync_to_host(lc, &nlive, llive, sizeof(nlive))) return join(e);
                 a.dense_form = (int64_t)nlive > lim ? 1 : 0;
@@ -2176,7 +2157,7 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
 #ifdef SKML_AB
             if (own_pass && launch_agg_bounds(ls, a.gk, v.nnz, v.g_dev, ntiles, dim, const_cast<int32_t*>(a.bounds), err,
                                               tile_bits) != hipSuccess)
-                return join(sfail(SKML_E_HIP, "agg_bounds launch failed"));
+                return join(fail(SKML_E_HIP, "agg_bounds launch failed"));
 #endif
             pays.push_back(a);
             ko += key_words(p);
@@ -2184,11 +2165,11 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
             bo += (int64_t)v.g.G * (ntiles + 1);
         }
         if (lanes[1]) {
-            SP_HIP(hipEventRecord(ev_join, side_st));
-            SP_HIP(hipStreamWaitEvent(st, ev_join, 0));
+            HIP_TRY(hipEventRecord(ev_join, side_st));
+            HIP_TRY(hipStreamWaitEvent(st, ev_join, 0));
         }
         const bool last = end == todo.size();
-        SP_HIP(hipMemcpyAsync(d_pays, pays.data(), sizeof(AggPayload) * pays.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_pays, pays.data(), sizeof(AggPayload) * pays.size(), hipMemcpyHostToDevice, st));
         // the wave-tile form takes 8 payloads per launch (a lane per (payload, group)); later
         // launches continue the sum in payload order
         const size_t chunk = vt ? (size_t)kAggVPayloads : pays.size();
@@ -2196,21 +2177,21 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
             const size_t nc = std::min(chunk, pays.size() - c0);
             bool any_dense = false;
             for (size_t q = c0; q < c0 + nc; q++) any_dense |= pays[q].dense_form != 0;
-            SP_HIP(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, first && c0 == 0 ? 0 : 1,
-                                    last && c0 + nc == pays.size() ? scale : 1.0, err, vt, gk, gbn, any_dense));
+            HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, first && c0 == 0 ? 0 : 1,
+                                     last && c0 + nc == pays.size() ? scale : 1.0, err, vt, gk, gbn, any_dense));
         }
-        SP_HIP(hipStreamSynchronize(st));  // `pays` (host) and the scratch are reused by the next batch
+        HIP_TRY(hipStreamSynchronize(st));  // `pays` (host) and the scratch are reused by the next batch
         first = false;
         at = end;
     }
     unsigned bad = 0;
     if (int e = sync_to_host(c, &bad, err, sizeof(bad))) return e;
     if (bad & 1u)
-        return sfail(SKML_E_ARG, "a payload holds a key outside [0, %lld), a non-ascending run or a bin outside its "
-                                 "values (SparseDoubleGradient requires ascending indices in range)", (long long)dim);
+        return fail(SKML_E_ARG, "a payload holds a key outside [0, %lld), a non-ascending run or a bin outside its "
+                                "values (SparseDoubleGradient requires ascending indices in range)", (long long)dim);
     if (bad & 2u)
-        return sfail(SKML_E_ARG, "requirement failed: Indices are not strictly increasing (a key repeated across a "
-                                 "payload's groups; SparseDoubleGradient.scala:12)");
+        return fail(SKML_E_ARG, "requirement failed: Indices are not strictly increasing (a key repeated across a "
+                                "payload's groups; SparseDoubleGradient.scala:12)");
     return SKML_OK;
 }
 
@@ -2231,12 +2212,12 @@ int skml_delta_encode(skml_ctx* c, const int32_t* keys, int64_t n, int32_t* num_
                       int64_t* n_flag_bits, int64_t* n_delta_bits, uint64_t* flag_words_dev,
                       uint64_t* delta_words_dev, int64_t words_cap) {
     if (!c || !keys || n <= 0 || !num_intervals || !flag_kind || !n_flag_bits || !n_delta_bits)
-        return sfail(SKML_E_ARG, "bad delta arguments");
-    if (n > (int64_t)INT32_MAX) return sfail(SKML_E_ARG, "n exceeds Java int");
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+        return fail(SKML_E_ARG, "bad delta arguments");
+    if (n > (int64_t)INT32_MAX) return fail(SKML_E_ARG, "n exceeds Java int");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     skml_sparse tmp;
-    tmp.device = ctx_device(c);
+    tmp.device = c->device;
     tmp.nnz = n;
     SpGroups& G = tmp.g;
     G.G = 1;
@@ -2249,7 +2230,7 @@ int skml_delta_encode(skml_ctx* c, const int32_t* keys, int64_t n, int32_t* num_
     const int64_t fwn = flag_words_max(n), dwn = delta_words_max(n);
     const size_t o_w = align_up(sizeof(SpGroups), 256);
     char* blk = static_cast<char*>(ctx_scratch(c, kSlotDeltaEnc, o_w + sizeof(uint64_t) * (size_t)(fwn + dwn)));
-    if (!need || !small || !blk) return sfail(SKML_E_OOM, "delta scratch");
+    if (!need || !small || !blk) return fail(SKML_E_OOM, "delta scratch");
     tmp.g_dev = reinterpret_cast<SpGroups*>(blk);
     uint64_t* fwd = reinterpret_cast<uint64_t*>(blk + o_w);
     uint64_t* dwd = fwd + fwn;
@@ -2257,13 +2238,13 @@ int skml_delta_encode(skml_ctx* c, const int32_t* keys, int64_t n, int32_t* num_
     tmp.g_dev = nullptr;  // scratch-owned
     if (rc) return rc;
     SpGroups* g_dev = reinterpret_cast<SpGroups*>(blk);
-    SP_HIP(hipMemsetAsync(small, 0, sizeof(uint32_t) * ((size_t)kMaxGroups * kDeltaHist + 1), st));
-    SP_HIP(launch_group_prep(st, keys, n, g_dev, need, small, small + kMaxGroups * kDeltaHist, nullptr, 0, nullptr,
-                             nullptr));
+    HIP_TRY(hipMemsetAsync(small, 0, sizeof(uint32_t) * ((size_t)kMaxGroups * kDeltaHist + 1), st));
+    HIP_TRY(launch_group_prep(st, keys, n, g_dev, need, small, small + kMaxGroups * kDeltaHist, nullptr, 0, nullptr,
+                              nullptr));
     if (int e = encode_delta_device(c, st, g_dev, keys, need, n, small, small + kMaxGroups * kDeltaHist, fwd, dwd))
         return e;
     if (int e = sync_to_host(c, &G, g_dev, sizeof(SpGroups))) return e;
-    if (G.status & kSpOrder) return sfail(SKML_E_ORDER, "Log for a non-positive key delta (keys must ascend strictly)");
+    if (G.status & kSpOrder) return fail(SKML_E_ORDER, "Log for a non-positive key delta (keys must ascend strictly)");
     *num_intervals = G.m[0];
     *flag_kind = G.kind[0];
     *n_flag_bits = G.fb[1];
@@ -2271,12 +2252,12 @@ int skml_delta_encode(skml_ctx* c, const int32_t* keys, int64_t n, int32_t* num_
     const int64_t fw = (G.fb[1] + 63) / 64, dw = (G.db[1] + 63) / 64;
     if (flag_words_dev || delta_words_dev) {
         if (fw > words_cap || dw > words_cap)
-            return sfail(SKML_E_ARG, "words_cap %lld < needed %lld", (long long)words_cap, (long long)std::max(fw, dw));
+            return fail(SKML_E_ARG, "words_cap %lld < needed %lld", (long long)words_cap, (long long)std::max(fw, dw));
         if (flag_words_dev && fw)
-            SP_HIP(hipMemcpyAsync(flag_words_dev, fwd, sizeof(uint64_t) * fw, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(flag_words_dev, fwd, sizeof(uint64_t) * fw, hipMemcpyDeviceToDevice, st));
         if (delta_words_dev && dw)
-            SP_HIP(hipMemcpyAsync(delta_words_dev, dwd, sizeof(uint64_t) * dw, hipMemcpyDeviceToDevice, st));
-        SP_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(delta_words_dev, dwd, sizeof(uint64_t) * dw, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return SKML_OK;
 }
@@ -2285,11 +2266,11 @@ int skml_delta_decode(skml_ctx* c, int64_t n, int32_t num_intervals, int32_t fla
                       int64_t n_flag_words, const uint64_t* delta_words, int64_t n_delta_words, int32_t* keys_dev) {
     if (!c || n <= 0 || !keys_dev || !(num_intervals == 1 || num_intervals == 2 || num_intervals == 4 ||
                                        num_intervals == 8 || num_intervals == 16))
-        return sfail(SKML_E_ARG, "bad delta decode arguments");
-    SP_HIP(hipSetDevice(ctx_device(c)));
-    hipStream_t st = ctx_stream(c);
+        return fail(SKML_E_ARG, "bad delta decode arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
     skml_sparse tmp;
-    tmp.device = ctx_device(c);
+    tmp.device = c->device;
     tmp.nnz = n;
     SpGroups& G = tmp.g;
     G.G = 1;
@@ -2308,8 +2289,8 @@ int skml_delta_decode(skml_ctx* c, int64_t n, int32_t num_intervals, int32_t fla
     tmp.n_flag_words = nfw;
     tmp.n_delta_words = ndw;
     int32_t* gb = scratch<int32_t>(c, kSlotGBins, (size_t)n);
-    if (!gb) return sfail(SKML_E_OOM, "delta scratch");
-    if (hipMalloc(&tmp.g_dev, sizeof(SpGroups)) != hipSuccess) return sfail(SKML_E_OOM, "group table");
+    if (!gb) return fail(SKML_E_OOM, "delta scratch");
+    if (hipMalloc(&tmp.g_dev, sizeof(SpGroups)) != hipSuccess) return fail(SKML_E_OOM, "group table");
     int rc = upload_groups(c, &tmp);
     if (!rc) rc = decode_groups(c, &tmp, keys_dev, gb, false);
     (void)hipStreamSynchronize(st);

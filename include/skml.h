@@ -390,6 +390,76 @@ int skml_zip_release_workspace(skml_ctx* ctx);
 /* Test hook: the halving rounds of the context's last successful skml_zip_encode_* (-1: no context). */
 int skml_debug_zip_rounds(skml_ctx* ctx);
 
+/* ---- Optimiser update (ml/objective/GradientDescent.scala:89-117, ml/objective/Adam.scala:27-77):
+ * the consumer of Gradient.sum, optimizer.update(bcGrad.value, weights)
+ * (ml/algorithm/GeneralizedLinearModel.scala:156) ----
+ *
+ * The gradient of element i is g_i = scale * x_i in double, where x_i is the sum of the P decoded
+ * payload values (from +0.0, in payload order, as the decode-sum kernels hold it before their float
+ * cast; the fused entries never round it to float), an array element, or a key's value.
+ *   SGD:   w_i -= g_i * lr                                   (the caller decays lr)
+ *   Adam:  m_t = beta1*m + (1-beta1)*g ;  v_t = beta2*v + ((1-beta2)*g)*g
+ *          w -= ((sqrt(1-beta2_t)*m_t) / ((1-beta1_t)*(sqrt(v_t)+eps))) * lr ;  m = m_t ;  v = v_t
+ * in double in exactly this order, without contraction; sqrt and / are correctly rounded.  The state
+ * w, m, v shares one type, the entry's suffix: _f64 is the reference's; _f32 state is widened on
+ * load, the update runs in double on the unrounded m_t and v_t, and each of w, m, v is rounded to
+ * float once, at its store.
+ * select: SKML_OPT_ALL updates every element (update(DenseDoubleGradient): with g = 0, m and v
+ * still decay and w still moves); SKML_OPT_LIVE only those with fabs(g_i) > 1e-8, every other
+ * element keeps w, m, v bit for bit (what toSparse hands update(SparseDoubleGradient));
+ * SKML_OPT_AUTO is toAuto (DenseDoubleGradient.scala:64-95): it counts the live elements first and
+ * takes ALL when nnz > dim * 2 / 3 in Java int arithmetic, LIVE otherwise; it costs a second pass
+ * over the input and synchronises for the count.  ALL and LIVE are one pass. */
+#define SKML_OPT_SGD 0
+#define SKML_OPT_ADAM 1
+#define SKML_OPT_ALL 0
+#define SKML_OPT_LIVE 1
+#define SKML_OPT_AUTO 2
+typedef struct skml_opt_params {
+    int32_t kind;   /* SKML_OPT_SGD | SKML_OPT_ADAM */
+    int32_t select; /* SKML_OPT_ALL | SKML_OPT_LIVE | SKML_OPT_AUTO */
+    double lr;
+    double beta1, beta2;     /* Adam.scala:20-21 */
+    double beta1_t, beta2_t; /* Adam.scala:22-23, advanced by the caller (Adam.scala:29-32) */
+    double eps;              /* Maths.EPS */
+} skml_opt_params;
+/* Adam, ALL, beta1 = beta1_t = 0.9, beta2 = beta2_t = 0.999, eps = 1e-8, lr = 0. */
+void skml_opt_params_default(skml_opt_params* p);
+
+/* Gradient.sum + timesBy + optimizer.update in one pass over P gathered dense payloads (a ZipML
+ * payload is one): the decode-sum's kernel forms with the update of w / m / v in place of the
+ * fp32 store.  payloads_dev / P / stride / n / scale and the header checks (read back first:
+ * magic, status with SKML_E_NAN, n, code width, stride) are skml_dense_decode_sum_f32's.  w_dev, m_dev,
+ * v_dev: n values each, 16-byte aligned, overlapping neither each other nor the payloads; m_dev and
+ * v_dev must be NULL for SGD.  SKML_E_ARG for a NULL context, misaligned or overlapping state, P
+ * outside [1, 16], n < 1, or lr / betas / eps that are not finite.  ALL and LIVE return with the
+ * update queued on the context's stream.  Timed under SKML_K_DECODE_SUM. */
+int skml_dense_decode_sum_step_f32(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride, int64_t n,
+                                   double scale, const skml_opt_params* params, float* w_dev, float* m_dev,
+                                   float* v_dev);
+int skml_dense_decode_sum_step_f64(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride, int64_t n,
+                                   double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
+                                   double* v_dev);
+/* The same update from a dense device array of n floats (g_fp64 = 0) or doubles, 16-byte aligned:
+ * the output of skml_sparse_decode_sum_f64 or skml_fixed_decode_sum_f32, or an uncompressed
+ * gradient.  Asynchronous unless AUTO. */
+int skml_opt_step_f32(skml_ctx* ctx, const void* g_dev, int32_t g_fp64, int64_t n, double scale,
+                      const skml_opt_params* params, float* w_dev, float* m_dev, float* v_dev);
+int skml_opt_step_f64(skml_ctx* ctx, const void* g_dev, int32_t g_fp64, int64_t n, double scale,
+                      const skml_opt_params* params, double* w_dev, double* m_dev, double* v_dev);
+/* update(SparseDoubleGradient, ...) (Adam.scala:63-77, GradientDescent.scala:111-117): nnz int32 keys
+ * and their values (floats, or doubles when vals_fp64) update w / m / v (dim values each) at the
+ * keys.  Precondition, not verified: the keys are strictly increasing (SparseDoubleGradient's
+ * invariant), so that no element has two owners; a key outside [0, dim) is skipped.  ALL updates
+ * every key, LIVE those with fabs(g) > 1e-8; AUTO is refused (SKML_E_ARG): the caller that built
+ * the key list has made toAuto's choice.  Asynchronous. */
+int skml_opt_step_kv_f32(skml_ctx* ctx, const int32_t* keys_dev, const void* vals_dev, int32_t vals_fp64, int64_t nnz,
+                         int64_t dim, double scale, const skml_opt_params* params, float* w_dev, float* m_dev,
+                         float* v_dev);
+int skml_opt_step_kv_f64(skml_ctx* ctx, const int32_t* keys_dev, const void* vals_dev, int32_t vals_fp64, int64_t nnz,
+                         int64_t dim, double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
+                         double* v_dev);
+
 /* ---- Host memory in and out (the JNI path: a JVM float[] on its way to a socket) ---- */
 
 /* Pinned host memory (hipHostMalloc): a Java direct ByteBuffer over it (JNI NewDirectByteBuffer)

@@ -4,18 +4,18 @@ The hot path (k=128 quantile sketch, bucket quantisation, packed codes, sparse k
 codec) runs in hand-written gfx950 HIP kernels in lib/libskml.so behind the C ABI of
 include/skml.h; this package mirrors the reference's Java surface over that ABI.
 """
-from . import _lib, fixed_point
+from . import _lib, fixed_point, optim
 from .compressor import DenseVectorCompressor
 from .constants import Constants, Parallel
 from .context import Context, alloc_aligned, get_context
 from .exceptions import QuantileSketchException, SketchMLException
-from .distributed import decode_sum_fixed_point
+from .distributed import decode_sum_fixed_point, decode_sum_update
 from .gradient import DenseDoubleGradient, FixedPointGradient, Kind, SketchGradient, SparseDoubleGradient, ZipGradient, compress
 from .quantization import QuantileQuantizer, QuantizationType, Quantizer, UniformQuantizer, ZipMLQuantizer
 from .sparse import (DeltaAdaptiveEncoder, GroupedMinMaxSketch, SparsePayload, SparseVectorCompressor, decode_sum,
                      encode_dense_as_sparse, encode_sparse, to_sparse)
 
-__all__ = ["ZipGradient", "ZipMLQuantizer", "FixedPointGradient", "compress", "decode_sum_fixed_point", "fixed_point", "Constants", "Parallel", "DenseDoubleGradient", "Kind", "SketchGradient", "SparseDoubleGradient", "Context", "DeltaAdaptiveEncoder", "DenseVectorCompressor", "GroupedMinMaxSketch", "SparsePayload",
+__all__ = ["optim", "decode_sum_update", "ZipGradient", "ZipMLQuantizer", "FixedPointGradient", "compress", "decode_sum_fixed_point", "fixed_point", "Constants", "Parallel", "DenseDoubleGradient", "Kind", "SketchGradient", "SparseDoubleGradient", "Context", "DeltaAdaptiveEncoder", "DenseVectorCompressor", "GroupedMinMaxSketch", "SparsePayload",
            "SparseVectorCompressor", "decode_sum", "encode_dense_as_sparse", "encode_sparse", "to_sparse", "QuantileQuantizer", "QuantizationType", "Quantizer", "UniformQuantizer",
            "QuantileSketchException", "SketchMLException", "get_context", "alloc_aligned"]
 

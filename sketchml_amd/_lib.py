@@ -74,6 +74,16 @@ class FixedHeader(C.Structure):
                 ("reserved", C.c_int64 * 2)]
 
 
+SKML_OPT_SGD, SKML_OPT_ADAM = 0, 1
+SKML_OPT_ALL, SKML_OPT_LIVE, SKML_OPT_AUTO = 0, 1, 2
+
+
+class OptParams(C.Structure):
+    """skml_opt_params (include/skml.h): one optimiser step's kind, selection and constants."""
+    _fields_ = [("kind", C.c_int32), ("select", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("beta1_t", C.c_double), ("beta2_t", C.c_double), ("eps", C.c_double)]
+
+
 class SparseGroup(C.Structure):
     _fields_ = [("size", C.c_int32), ("col_num", C.c_int32), ("hash_ids", C.c_int32 * 8),
                 ("num_intervals", C.c_int32), ("flag_kind", C.c_int32),
@@ -145,6 +155,13 @@ _SIGS = {
     "skml_debug_zip_prefix_f64": (C.c_int, [vp, vp, i64, vp, vp, vp]),
     "skml_debug_zip_rounds": (C.c_int, [vp]),
     "skml_zip_release_workspace": (C.c_int, [vp]),
+    "skml_opt_params_default": (None, [C.POINTER(OptParams)]),
+    "skml_dense_decode_sum_step_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_dense_decode_sum_step_f64": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_opt_step_f32": (C.c_int, [vp, vp, i32, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_opt_step_f64": (C.c_int, [vp, vp, i32, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_opt_step_kv_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_opt_step_kv_f64": (C.c_int, [vp, vp, vp, i32, i64, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
     "skml_host_free": (C.c_int, [vp]),
     "skml_dense_encode_host_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), vp, C.c_size_t, szp]),

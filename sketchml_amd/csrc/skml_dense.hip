@@ -6,6 +6,7 @@
 // The sketch build (leaf / merge / summary) lives in skml_sketch.hip.
 #include <algorithm>
 
+#include "skml_codes.hpp"
 #include "skml_device.hpp"
 
 namespace skml {
@@ -352,16 +353,7 @@ hipError_t launch_quantize(hipStream_t st, const void* x, int64_t n, void* paylo
 // =============================================================================================
 // Decode: LUT of Quantizer.getValues() midpoints (computed in double, Quantizer.java:39-47).
 // =============================================================================================
-__device__ __forceinline__ uint32_t read_code(const uint8_t* codes, int64_t e, int bits) {
-    switch (bits) {
-        case 8: return codes[e];
-        case 16: return reinterpret_cast<const uint16_t*>(codes)[e];
-        case 4: return (codes[e >> 1] >> ((e & 1) * 4)) & 15u;
-        case 2: return (codes[e >> 2] >> ((e & 3) * 2)) & 3u;
-        default: return (codes[e >> 3] >> (e & 7)) & 1u;
-    }
-}
-
+// (read_code and lut_value: skml_codes.hpp)
 // Four consecutive codes starting at e0 (multiple of 4).
 __device__ __forceinline__ void read_codes4(const uint8_t* codes, int64_t e0, int bits, uint32_t (&c)[4]) {
     switch (bits) {
@@ -391,13 +383,6 @@ __device__ __forceinline__ void read_codes4(const uint8_t* codes, int64_t e0, in
             break;
         }
     }
-}
-
-__device__ __forceinline__ double lut_value(const skml_dense_header* h, const double* sp, int b) {
-    const int ns = h->bin_num - 1;
-    if (b == 0) return 0.5 * (h->min + sp[0]);
-    if (b == ns) return 0.5 * (sp[ns - 1] + h->max);
-    return 0.5 * (sp[b - 1] + sp[b]);
 }
 
 constexpr int kLutMax = 4096;
@@ -484,9 +469,8 @@ hipError_t launch_decode(hipStream_t st, const void* payload, void* out, int64_t
 
 // Fused decode of P payloads + sum in double (Gradient.sum adds doubles) + scale.  Payloads of at
 // most kSumLutBins bins look their values up in an LDS table; wider ones (16-bit codes) compute
-// the midpoint from the payload's splits, as k_decode does above kLutMax.
-constexpr int kMaxSumPayloads = 16;
-constexpr int kSumLutBins = 256;
+// the midpoint from the payload's splits, as k_decode does above kLutMax.  (kMaxSumPayloads,
+// kSumLutBins, kSumChunk: skml_codes.hpp)
 // 16 consecutive codes of one payload starting at e0 (a multiple of 16): one load of 2..32 bytes.
 __device__ __forceinline__ void load_codes16(const uint8_t* codes, int64_t e0, int bits, uint32_t (&w)[8]) {
     switch (bits) {
@@ -526,7 +510,6 @@ __device__ __forceinline__ uint32_t code16_at(const uint32_t (&w)[8], int e, int
 // into 16 double accumulators (Gradient.sum adds doubles in gradient order), the next 8 payloads
 // likewise, and stores 64 contiguous bytes of fp32 (nontemporal).  BITS: the code width when all
 // payloads share it (the common case: one bin count), 0 = per payload.
-constexpr int kSumChunk = 8;
 // A lane's N (8 or 16) sums as 16-bit values: (float)(acc * scale) as in the fp32 form, rounded to
 // nearest even; one or two 16-byte nontemporal stores (vec: `out` is 16-byte aligned), element
 // stores otherwise.
@@ -671,59 +654,8 @@ __global__ __launch_bounds__(256) void k_decode_sum(const uint8_t* __restrict__ 
 // the bank conflicts and ran slower (412 against 355 us at C4) for the same reason.  Here a lane
 // owns 8 elements (half the registers of k_decode_sum: 8 waves per SIMD), the tables take
 // P x bins doubles of dynamic LDS instead of a 32 KB array, and the next step's codes are loaded
-// before this step's lookups.
-#ifndef SKML_OCC_WAVES
-#define SKML_OCC_WAVES 4  // waves per SIMD of the prefetching form, 8- and 16-bit codes (4 against 6 and 8: profiles/ab/r06_occ_waves.txt)
-#endif
-#ifndef SKML_OCC_WAVES_NARROW
-// the same for 1-, 2- and 4-bit codes: a step then loads 1-4 bytes per payload and lane, so the
-// codes need more waves in flight (C5's 2-bit sum ran 154 us at 6 and 253 us at 4, profiles/ab/r06_occ_narrow.txt)
-#define SKML_OCC_WAVES_NARROW 6
-#endif
-#ifndef SKML_OCC_PER
-#define SKML_OCC_PER 8  // elements per lane and step (A/B builds: 16)
-#endif
-constexpr int kOccPer = SKML_OCC_PER, kOccMaxP = 8;
-static_assert(kOccPer == 8 || kOccPer == 16, "8 or 16 elements per lane");
-// dynamic LDS of the P tables: what is left of the 64 KB a launch may take without opting in
-// after the kernel's static array of code pointers
-constexpr size_t kOccLdsMax = 64 * 1024 - sizeof(const uint8_t*) * kOccMaxP;
-// code words one lane holds per payload and step
-template <int BITS>
-constexpr int occ_words() { return kOccPer * BITS >= 32 ? kOccPer * BITS / 32 : 1; }
-// The code loads go through a global (address space 1) pointer: the payloads' code pointers sit in
-// LDS, and loads through a generic pointer would be flat loads, which count on lgkmcnt too, so the
-// table lookups' LDS waits would also wait for the next step's prefetched codes.
-#define SKML_G(T) const __attribute__((address_space(1))) T*
-template <int BITS>
-__device__ __forceinline__ void load_codes_occ(const uint8_t* codes_any, int64_t e0, uint32_t (&w)[occ_words<BITS>()]) {
-    SKML_G(uint8_t) codes = (SKML_G(uint8_t))codes_any;
-    constexpr int kBytes = kOccPer * BITS / 8;  // e0 is a multiple of kOccPer: aligned to kBytes
-    const int64_t b0 = e0 * BITS / 8;
-    typedef uint32_t u32x4_g __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2_g __attribute__((ext_vector_type(2)));
-    if constexpr (kBytes >= 16) {
-#pragma unroll
-        for (int q = 0; q < kBytes / 16; q++) {
-            const u32x4_g v = *(SKML_G(u32x4_g))(codes + b0 + 16 * q);
-            w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-        }
-    } else if constexpr (kBytes == 8) {
-        const u32x2_g v = *(SKML_G(u32x2_g))(codes + b0);
-        w[0] = v.x; w[1] = v.y;
-    } else if constexpr (kBytes == 4) {
-        w[0] = *(SKML_G(uint32_t))(codes + b0);
-    } else if constexpr (kBytes == 2) {
-        w[0] = *(SKML_G(uint16_t))(codes + b0);
-    } else {
-        w[0] = codes[b0];
-    }
-}
-#undef SKML_G
-template <int BITS>
-__device__ __forceinline__ uint32_t code_occ_at(const uint32_t (&w)[occ_words<BITS>()], int e) {
-    return (w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u);
-}
+// before this step's lookups.  (SKML_OCC_WAVES*, kOccPer, kOccLdsMax and the code loads:
+// skml_codes.hpp)
 template <int BITS, bool PF, typename O = float>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF ? (BITS >= 8 ? SKML_OCC_WAVES : SKML_OCC_WAVES_NARROW) : 8))) void k_decode_sum_occ(
     const uint8_t* __restrict__ payloads, int P, size_t stride, O* __restrict__ out, int64_t n, double scale,

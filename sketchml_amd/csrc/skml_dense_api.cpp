@@ -783,10 +783,11 @@ int skml_dense_decode_f16(skml_ctx* c, const void* payload, uint16_t* out, int64
     return dense_decode_lowp(c, payload, out, n, kXF16);
 }
 
-static int dense_decode_sum_x(skml_ctx* c, const void* payloads, int32_t P, size_t stride, void* out, int otype,
-                              int64_t n, double scale) {
-    if (!c || !valid_payload_ptr(payloads) || stride % 256 || P < 1 || P > 16 ||
-        (n > 0 && (!out || ((uintptr_t)out) % (otype == kXF32 ? 16 : 2))))
+}  // extern "C"
+
+int skml::dense_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* common_bits_out,
+                            int* max_bins_out) {
+    if (!c || !valid_payload_ptr(payloads) || stride % 256 || P < 1 || P > 16)
         return fail(SKML_E_ARG, "bad decode_sum arguments (P in [1,16], 256-B aligned payloads)");
     HIP_TRY(hipSetDevice(c->device));
     // Gradient.sum adds gradients of one dimension (ml/gradient/Gradient.scala:44-49): every
@@ -815,6 +816,19 @@ static int dense_decode_sum_x(skml_ctx* c, const void* payloads, int32_t P, size
         if (h[p].code_bits != common_bits) common_bits = 0;
         max_bins = std::max(max_bins, (int)h[p].bin_num);
     }
+    *common_bits_out = common_bits;
+    *max_bins_out = max_bins;
+    return SKML_OK;
+}
+
+extern "C" {
+
+static int dense_decode_sum_x(skml_ctx* c, const void* payloads, int32_t P, size_t stride, void* out, int otype,
+                              int64_t n, double scale) {
+    if (c && n > 0 && (!out || ((uintptr_t)out) % (otype == kXF32 ? 16 : 2)))
+        return fail(SKML_E_ARG, "bad decode_sum arguments (P in [1,16], 256-B aligned payloads)");
+    int common_bits = 0, max_bins = 0;
+    if (const int st = dense_sum_headers(c, payloads, P, stride, n, &common_bits, &max_bins)) return st;
     KernelTimer kt(c, SKML_K_DECODE_SUM);
     HIP_TRY(launch_decode_sum(c->stream, payloads, P, stride, out, n, scale, common_bits, max_bins, otype));
     return SKML_OK;

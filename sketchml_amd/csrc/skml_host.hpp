@@ -53,6 +53,7 @@ struct skml_ctx {
     skml::FxPartial* fx_part = nullptr;
     skml::DevBuf zip_ws;  // ZipMLQuantizer: keys, sorted copy, prefix sums, errors, splitIndex
     int zip_rounds = 0;   // halving rounds of the last successful ZipML encode (skml_debug_zip_rounds)
+    skml::DevBuf opt_ws;  // optimiser step: the live counter of SKML_OPT_AUTO
     skml::DevBuf stage;   // staging
     // sparse path: device scratch slots and pinned host staging
     skml::DevBuf scratch[skml::kScratchSlots];
@@ -151,5 +152,12 @@ struct Workspace {
     LeafPartial* part_red;  // leaf partials reduced per first-pass merge workgroup
 };
 int ensure_ws(skml_ctx* ctx, int64_t chunks, Workspace* w);
+
+// What every consumer of P gathered dense payloads checks first (skml_dense_decode_sum_*, the fused
+// optimiser step): the context and the payload arguments, then the P headers read back through the
+// pinned staging (synchronises): magic, status (SKML_E_NAN), n, code width, stride.
+// *common_bits: the payloads' code width, 0 when they differ; *max_bins: the largest table.
+int dense_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* common_bits,
+                      int* max_bins);
 
 }  // namespace skml

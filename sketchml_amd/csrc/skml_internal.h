@@ -212,6 +212,36 @@ hipError_t launch_fixed_decode_sum(hipStream_t st, const void* payloads, int P, 
                                    int64_t n, double scale, int bits);
 hipError_t launch_fixed_codes(hipStream_t st, const void* payload, int32_t* codes, int64_t n);
 hipError_t launch_fixed_times_by(hipStream_t st, void* payload, double x);
+// ---- optimiser update (skml_optim.hip; ml/objective/GradientDescent.scala, Adam.scala) ----
+// What the update kernels take by value: the step's constants, computed once on the host in the
+// reference's double arithmetic (Adam.scala:54-57).
+struct OptConsts {
+    double lr;
+    double beta1, beta2;
+    double omb1, omb2;  // 1 - beta1, 1 - beta2
+    double c_m;         // Math.sqrt(1 - beta2_t)
+    double c_d;         // 1 - beta1_t
+    double eps;
+    int32_t live;       // 1: only elements with |g| > 1e-8 are touched
+    int32_t adam;
+};
+constexpr int kOptPer = 8;  // elements per lane and step of the dense update kernels
+// w / m / v: n values of float (wide = 0) or double, 16-byte aligned; m, v null for SGD.
+// common_bits / max_bins as launch_decode_sum.
+hipError_t launch_decode_sum_step(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n, double scale,
+                                  int common_bits, int max_bins, const OptConsts& k, int wide, void* w, void* m,
+                                  void* v);
+// *count (zeroed by the caller on the same stream) += #{i : |scale * sum_p v_p[i]| > 1e-8}
+hipError_t launch_decode_sum_live(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n, double scale,
+                                  unsigned long long* count);
+// g: n values of float (g_wide = 0) or double, 16-byte aligned
+hipError_t launch_opt_step(hipStream_t st, const void* g, int g_wide, int64_t n, double scale, const OptConsts& k,
+                           int wide, void* w, void* m, void* v);
+hipError_t launch_opt_count(hipStream_t st, const void* g, int g_wide, int64_t n, double scale,
+                            unsigned long long* count);
+// keys strictly increasing (not verified; a key outside [0, dim) is skipped)
+hipError_t launch_opt_step_kv(hipStream_t st, const int32_t* keys, const void* vals, int v_wide, int64_t nnz,
+                              int64_t dim, double scale, const OptConsts& k, int wide, void* w, void* m, void* v);
 // ---- ZipMLQuantizer (skml_zip.hip) ----
 constexpr int kZipMinBins = 4;   // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
 constexpr int kZipTail = 4096;   // splitNum at which the rounds move into one workgroup's LDS

@@ -153,6 +153,20 @@ def decode_sum(ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, n: 
                                 C.c_void_p(out.data_ptr()), n, float(scale)), "decode_sum")
 
 
+def decode_sum_update(ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, n: int, scale: float,
+                      optimizer, weight: torch.Tensor, select: int = _lib.SKML_OPT_ALL) -> None:
+    """The fused consumer of the all-gather: decode_sum and optimizer.update(sum, weight)
+    (GeneralizedLinearModel.scala:145-156) in one pass over the gathered dense payloads
+    (skml_dense_decode_sum_step_f32 / _f64, by the weight's dtype).  The sum stays in double, is never
+    stored and never rounded to float.  `optimizer` is an optim.GradientDescent or optim.Adam of
+    dim n; like its update() this advances Adam's beta_t at the first batch of a later epoch.  The
+    default selection updates every element, as update(DenseDoubleGradient) of Gradient.sum's result."""
+    if int(n) != optimizer.dim:
+        raise SketchMLException(f"decode_sum_update: n={n}, the optimiser's dim is {optimizer.dim}")
+    optimizer._begin_update()
+    optimizer.step_payloads(ctx_handle, payloads, nranks, stride, scale, weight, select)
+
+
 _DECODE_SUM = {torch.float32: "skml_dense_decode_sum_f32", torch.bfloat16: "skml_dense_decode_sum_bf16",
                torch.float16: "skml_dense_decode_sum_f16"}
 

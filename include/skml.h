@@ -440,6 +440,20 @@ int skml_dense_decode_sum_step_f32(skml_ctx* ctx, const void* payloads_dev, int3
 int skml_dense_decode_sum_step_f64(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride, int64_t n,
                                    double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
                                    double* v_dev);
+/* The same for P gathered FixedPointGradient payloads: skml_fixed_decode_sum_f32's walk with the update
+ * of w / m / v in place of its (float)(scale * sum) store, so the gradient is the double the
+ * reference's update(fpGrad.toAuto, weight) sees.  payloads_dev / P / stride / n / scale and the
+ * header checks (read back first: magic, status with SKML_E_NAN, n, one num_bits, stride) are
+ * skml_fixed_decode_sum_f32's; params, the state and their checks are skml_dense_decode_sum_step_*'s,
+ * the payloads' range being [payloads_dev, payloads_dev + (P - 1) * stride + skml_fixed_payload_bytes(n,
+ * num_bits)).  LIVE and AUTO as above (AUTO's count pass walks the payloads once more and
+ * synchronises).  Timed under SKML_K_DECODE_SUM. */
+int skml_fixed_decode_sum_step_f32(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride, int64_t n,
+                                   double scale, const skml_opt_params* params, float* w_dev, float* m_dev,
+                                   float* v_dev);
+int skml_fixed_decode_sum_step_f64(skml_ctx* ctx, const void* payloads_dev, int32_t P, size_t stride, int64_t n,
+                                   double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
+                                   double* v_dev);
 /* The same update from a dense device array of n floats (g_fp64 = 0) or doubles, 16-byte aligned:
  * the output of skml_sparse_decode_sum_f64 or skml_fixed_decode_sum_f32, or an uncompressed
  * gradient.  Asynchronous unless AUTO. */

@@ -9,13 +9,13 @@ from .compressor import DenseVectorCompressor
 from .constants import Constants, Parallel
 from .context import Context, alloc_aligned, get_context
 from .exceptions import QuantileSketchException, SketchMLException
-from .distributed import decode_sum_fixed_point, decode_sum_update
+from .distributed import decode_sum_fixed_point, decode_sum_update, decode_sum_update_fixed_point
 from .gradient import DenseDoubleGradient, FixedPointGradient, Kind, SketchGradient, SparseDoubleGradient, ZipGradient, compress
 from .quantization import QuantileQuantizer, QuantizationType, Quantizer, UniformQuantizer, ZipMLQuantizer
 from .sparse import (DeltaAdaptiveEncoder, GroupedMinMaxSketch, SparsePayload, SparseVectorCompressor, decode_sum,
                      encode_dense_as_sparse, encode_sparse, to_sparse)
 
-__all__ = ["optim", "decode_sum_update", "ZipGradient", "ZipMLQuantizer", "FixedPointGradient", "compress", "decode_sum_fixed_point", "fixed_point", "Constants", "Parallel", "DenseDoubleGradient", "Kind", "SketchGradient", "SparseDoubleGradient", "Context", "DeltaAdaptiveEncoder", "DenseVectorCompressor", "GroupedMinMaxSketch", "SparsePayload",
+__all__ = ["optim", "decode_sum_update", "decode_sum_update_fixed_point", "ZipGradient", "ZipMLQuantizer", "FixedPointGradient", "compress", "decode_sum_fixed_point", "fixed_point", "Constants", "Parallel", "DenseDoubleGradient", "Kind", "SketchGradient", "SparseDoubleGradient", "Context", "DeltaAdaptiveEncoder", "DenseVectorCompressor", "GroupedMinMaxSketch", "SparsePayload",
            "SparseVectorCompressor", "decode_sum", "encode_dense_as_sparse", "encode_sparse", "to_sparse", "QuantileQuantizer", "QuantizationType", "Quantizer", "UniformQuantizer",
            "QuantileSketchException", "SketchMLException", "get_context", "alloc_aligned"]
 

@@ -158,6 +158,8 @@ _SIGS = {
     "skml_opt_params_default": (None, [C.POINTER(OptParams)]),
     "skml_dense_decode_sum_step_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_dense_decode_sum_step_f64": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_fixed_decode_sum_step_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_fixed_decode_sum_step_f64": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_opt_step_f32": (C.c_int, [vp, vp, i32, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_opt_step_f64": (C.c_int, [vp, vp, i32, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_opt_step_kv_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),

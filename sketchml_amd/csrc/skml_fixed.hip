@@ -4,6 +4,9 @@
 //   k_fixed_quantize                code = floor(|v| / norm * max) + sigma | sign, packed MSB-first
 //                                   into the BitSet word stream
 //   k_fixed_decode, k_fixed_decode_sum, k_fixed_codes, k_fixed_times_by
+//   k_fixed_decode_sum_step         the decode-sum's walk with the optimiser update of w / m / v in place
+//                                   of the fp32 store: the gradient stays the unrounded double
+//   k_fixed_decode_sum_live         #{|g| > 1e-8} of the same sums (toAuto's count)
 // Every pass streams: 16-byte nontemporal loads of the values, whole 64-bit words of the stream.
 // A staging round is 1,024 consecutive elements = exactly 16 b whole words for every width b, so no
 // word is shared between waves and nothing is atomic; a wave owns four consecutive rounds (4,096
@@ -11,6 +14,7 @@
 #include <algorithm>
 
 #include "skml_device.hpp"
+#include "skml_opt.hpp"
 
 namespace skml {
 
@@ -28,7 +32,7 @@ constexpr int kFxLutBits = 8;           // decode: widths up to this look their 
 #define SKML_FX_D_WAVES 4
 #endif
 #ifndef SKML_FX_S_WAVES
-#define SKML_FX_S_WAVES 3  // the decode-sum's form for widths 2, 4, 8, 16 (4 spills); the general form keeps 2
+#define SKML_FX_S_WAVES 3  // the decode-sum's forms (sum, step, live) for widths 2, 4, 8, 16 (4 spills); the general forms keep 2
 #endif
 
 template <typename X>
@@ -408,13 +412,13 @@ hipError_t launch_fixed_decode(hipStream_t st, const void* payload, void* out, i
 // one aligned 4 b-bit piece of the stage (one LDS read instead of four to eight).  (The lanes
 // loading their pieces straight from the stream, without the stage, ran twice as long: 2.11
 // against 1.11 ms for 8 payloads of 2^28 8-bit codes.)
+// The walk is one function for its three consumers: done(sb, full, lane, acc) gets the round's
+// unscaled sums, acc[4 m + k] of element sb + (64 m + lane) 4 + k, and is reached by every lane of
+// the wave; `full` says that the round lies inside n.
 constexpr int kFxMaxSumPayloads = 16;
-template <bool POW2>
-__global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2 ? SKML_FX_S_WAVES : 2))) void k_fixed_decode_sum(
-    const uint8_t* __restrict__ payloads, int P, size_t stride, float* __restrict__ out, int64_t n, double scale, int b) {
-    __shared__ uint64_t stage[kFxWaves][kFxSubWordsMax];
-    __shared__ double s_norm[kFxMaxSumPayloads];
-    extern __shared__ double slut[];  // P << b doubles when b <= kFxLutBits
+template <bool POW2, typename F>
+__device__ __forceinline__ void fx_sum_rounds(const uint8_t* __restrict__ payloads, int P, size_t stride, int64_t n, int b,
+                                              uint64_t (*stage)[kFxSubWordsMax], double* s_norm, double* slut, F&& done) {
     const uint32_t sign = 1u << (b - 1), maxv = sign - 1u, fmask = (sign << 1) - 1u;
     const double dmax = (double)maxv;
     const bool use_lut = b <= kFxLutBits;
@@ -432,7 +436,6 @@ __global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2
     const int64_t nwaves = (int64_t)gridDim.x * kFxWaves, wid = (int64_t)blockIdx.x * kFxWaves + wave;
     const int64_t subs = (n + kFxSub - 1) / kFxSub;
     const int nw = 16 * b;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     auto words_of = [&](int p) {
         return reinterpret_cast<const uint64_t*>(payloads + (size_t)p * stride + kFxHeaderBytes);
     };
@@ -469,7 +472,19 @@ __global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2
             __builtin_amdgcn_wave_barrier();  // the stage is read before the next payload overwrites it
         }
         const int64_t sb = s * kFxSub;
-        const bool full = sb + kFxSub <= n;
+        done(sb, sb + kFxSub <= n, lane, acc);
+    }
+}
+
+template <bool POW2>
+__global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2 ? SKML_FX_S_WAVES : 2))) void k_fixed_decode_sum(
+    const uint8_t* __restrict__ payloads, int P, size_t stride, float* __restrict__ out, int64_t n, double scale, int b) {
+    __shared__ uint64_t stage[kFxWaves][kFxSubWordsMax];
+    __shared__ double s_norm[kFxMaxSumPayloads];
+    extern __shared__ double slut[];  // P << b doubles when b <= kFxLutBits
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    fx_sum_rounds<POW2>(payloads, P, stride, n, b, stage, s_norm, slut,
+                        [&](int64_t sb, bool full, int lane, const double (&acc)[16]) {
 #pragma unroll
         for (int m = 0; m < 4; m++) {
             const f32x4 o = {(float)(acc[4 * m] * scale), (float)(acc[4 * m + 1] * scale), (float)(acc[4 * m + 2] * scale),
@@ -483,20 +498,123 @@ __global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2
                     if (e0 + k < n) out[e0 + k] = o[k];
             }
         }
-    }
+    });
+}
+
+// The same walk with the optimiser update in place of the fp32 store (skml_opt.hpp): g = acc * scale
+// stays the double it is.  A lane owns four consecutive elements per m step -- one 16-byte vector of
+// fp32 state, two of fp64 -- and takes the state one m step at a time, so that at most four
+// elements' w, m, v are live beside the 16 sums.  Every element has one owner: the update is in
+// place.  LIVE: a full vector whose four elements are all dead (|g| <= 1e-8) is not stored; the
+// partial last round goes element by element.  The waves asked for are the decode-sum's: the
+// aligned-piece forms take 140-143 registers, which is 3 waves whether 2 or 3 are asked for, and
+// spill 44-52 bytes per lane at 4.
+template <bool POW2, typename W, bool ADAM>
+__global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2 ? SKML_FX_S_WAVES : 2))) void k_fixed_decode_sum_step(
+    const uint8_t* __restrict__ payloads, int P, size_t stride, int64_t n, double scale, int b, OptConsts k,
+    W* __restrict__ pw, W* __restrict__ pm, W* __restrict__ pv) {
+    __shared__ uint64_t stage[kFxWaves][kFxSubWordsMax];
+    __shared__ double s_norm[kFxMaxSumPayloads];
+    extern __shared__ double slut[];
+    fx_sum_rounds<POW2>(payloads, P, stride, n, b, stage, s_norm, slut,
+                        [&](int64_t sb, bool full, int lane, const double (&acc)[16]) {
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+            const double g[4] = {acc[4 * m] * scale, acc[4 * m + 1] * scale, acc[4 * m + 2] * scale, acc[4 * m + 3] * scale};
+            const int64_t e0 = sb + (m * 64 + lane) * 4;
+            if (full) {
+                StateN<ADAM, W, 4> st;
+                st.load(pw, pm, pv, e0);
+                st.apply(g, k);
+                if (!k.live || fabs(g[0]) > 1e-8 || fabs(g[1]) > 1e-8 || fabs(g[2]) > 1e-8 || fabs(g[3]) > 1e-8)
+                    st.store(pw, pm, pv, e0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (e0 + j < n) opt_apply_at<ADAM>(g[j], pw, pm, pv, e0 + j, k);
+            }
+        }
+    });
+}
+
+// #{|g| > 1e-8} of the same sums into *count (toAuto's count, as k_decode_sum_live's for dense
+// payloads).  The rounds are the wave's, so every lane reaches every ballot.
+template <bool POW2>
+__global__ __launch_bounds__(kFxThreads) __attribute__((amdgpu_waves_per_eu(POW2 ? SKML_FX_S_WAVES : 2))) void k_fixed_decode_sum_live(
+    const uint8_t* __restrict__ payloads, int P, size_t stride, int64_t n, double scale, int b, unsigned long long* count) {
+    __shared__ uint64_t stage[kFxWaves][kFxSubWordsMax];
+    __shared__ double s_norm[kFxMaxSumPayloads];
+    __shared__ unsigned long long s_cnt;
+    extern __shared__ double slut[];
+    LiveCount lc;
+    fx_sum_rounds<POW2>(payloads, P, stride, n, b, stage, s_norm, slut,
+                        [&](int64_t sb, bool full, int lane, const double (&acc)[16]) {
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+            lc.add((full || sb + ((e >> 2) * 64 + lane) * 4 + (e & 3) < n) && fabs(acc[e] * scale) > 1e-8);
+    });
+    lc.finish(&s_cnt, count);
+}
+
+static size_t fx_sum_lds(int P, int bits) { return bits <= kFxLutBits ? sizeof(double) * ((size_t)P << bits) : 0; }
+static bool fx_pow2(int bits) { return bits == 2 || bits == 4 || bits == 8 || bits == 16; }
+static bool fx_sum_args_ok(int P, int bits) {
+    return P >= 1 && P <= kFxMaxSumPayloads && bits >= kFxMinBits && bits <= kFxMaxBits;
 }
 
 hipError_t launch_fixed_decode_sum(hipStream_t st, const void* payloads, int P, size_t stride, float* out,
                                    int64_t n, double scale, int bits) {
     if (n <= 0) return hipSuccess;
-    if (P < 1 || P > kFxMaxSumPayloads || bits < kFxMinBits || bits > kFxMaxBits) return hipErrorInvalidValue;
-    const size_t lds = bits <= kFxLutBits ? sizeof(double) * ((size_t)P << bits) : 0;
-    if (bits == 2 || bits == 4 || bits == 8 || bits == 16)
+    if (!fx_sum_args_ok(P, bits)) return hipErrorInvalidValue;
+    const size_t lds = fx_sum_lds(P, bits);
+    if (fx_pow2(bits))
         hipLaunchKernelGGL(k_fixed_decode_sum<true>, dim3(fx_stream_grid(n)), dim3(kFxThreads), lds, st,
                            reinterpret_cast<const uint8_t*>(payloads), P, stride, out, n, scale, bits);
     else
         hipLaunchKernelGGL(k_fixed_decode_sum<false>, dim3(fx_stream_grid(n)), dim3(kFxThreads), lds, st,
                            reinterpret_cast<const uint8_t*>(payloads), P, stride, out, n, scale, bits);
+    return hipGetLastError();
+}
+
+template <bool POW2, typename W>
+static void launch_fixed_step_w(hipStream_t st, const uint8_t* pl, int P, size_t stride, int64_t n, double scale, int bits,
+                                const OptConsts& k, void* w, void* m, void* v) {
+    const dim3 grid(fx_stream_grid(n)), block(kFxThreads);
+    const size_t lds = fx_sum_lds(P, bits);
+    if (k.adam)
+        hipLaunchKernelGGL((k_fixed_decode_sum_step<POW2, W, true>), grid, block, lds, st, pl, P, stride, n, scale, bits, k,
+                           static_cast<W*>(w), static_cast<W*>(m), static_cast<W*>(v));
+    else
+        hipLaunchKernelGGL((k_fixed_decode_sum_step<POW2, W, false>), grid, block, lds, st, pl, P, stride, n, scale, bits, k,
+                           static_cast<W*>(w), static_cast<W*>(m), static_cast<W*>(v));
+}
+
+hipError_t launch_fixed_decode_sum_step(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n,
+                                        double scale, int bits, const OptConsts& k, int wide, void* w, void* m, void* v) {
+    if (n <= 0) return hipSuccess;
+    if (!fx_sum_args_ok(P, bits)) return hipErrorInvalidValue;
+    const uint8_t* pl = reinterpret_cast<const uint8_t*>(payloads);
+    if (fx_pow2(bits)) {
+        if (wide) launch_fixed_step_w<true, double>(st, pl, P, stride, n, scale, bits, k, w, m, v);
+        else launch_fixed_step_w<true, float>(st, pl, P, stride, n, scale, bits, k, w, m, v);
+    } else {
+        if (wide) launch_fixed_step_w<false, double>(st, pl, P, stride, n, scale, bits, k, w, m, v);
+        else launch_fixed_step_w<false, float>(st, pl, P, stride, n, scale, bits, k, w, m, v);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_decode_sum_live(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n,
+                                        double scale, int bits, unsigned long long* count) {
+    if (n <= 0) return hipSuccess;
+    if (!fx_sum_args_ok(P, bits)) return hipErrorInvalidValue;
+    const uint8_t* pl = reinterpret_cast<const uint8_t*>(payloads);
+    if (fx_pow2(bits))
+        hipLaunchKernelGGL(k_fixed_decode_sum_live<true>, dim3(fx_stream_grid(n)), dim3(kFxThreads), fx_sum_lds(P, bits), st,
+                           pl, P, stride, n, scale, bits, count);
+    else
+        hipLaunchKernelGGL(k_fixed_decode_sum_live<false>, dim3(fx_stream_grid(n)), dim3(kFxThreads), fx_sum_lds(P, bits), st,
+                           pl, P, stride, n, scale, bits, count);
     return hipGetLastError();
 }
 

@@ -66,30 +66,12 @@ int skml_fixed_decode_f64(skml_ctx* c, const void* payload, double* out, int64_t
 
 int skml_fixed_decode_sum_f32(skml_ctx* c, const void* payloads, int32_t P, size_t stride, float* out, int64_t n,
                               double scale) {
-    if (!c || !valid_payload_ptr(payloads) || stride % 256 || P < 1 || P > 16 || n < 1 || !out || ((uintptr_t)out) % 16)
+    if (c && (!out || ((uintptr_t)out) % 16))
         return fail(SKML_E_ARG, "bad decode_sum arguments (P in [1,16], 256-B aligned payloads)");
-    HIP_TRY(hipSetDevice(c->device));
-    // the headers come back through the context's pinned staging, as in skml_dense_decode_sum_f32
-    skml_fixed_header* h = static_cast<skml_fixed_header*>(skml::ctx_pinned(c, sizeof(skml_fixed_header) * 16));
-    if (!h) return fail(SKML_E_OOM, "pinned staging of the payload headers");
-    for (int p = 0; p < P; p++)
-        HIP_TRY(hipMemcpyAsync(h + p, static_cast<const char*>(payloads) + (size_t)p * stride, sizeof(skml_fixed_header),
-                               hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int p = 0; p < P; p++) {
-        if (h[p].magic != SKML_FIXED_MAGIC) return fail(SKML_E_STATE, "payload %d is not a fixed-point payload", p);
-        if (h[p].status == SKML_E_NAN) return fail(SKML_E_NAN, "payload %d: NaN, infinite or underflowed input", p);
-        if (h[p].status != SKML_OK) return fail(SKML_E_STATE, "payload %d has status %d", p, h[p].status);
-        if (h[p].n != n)
-            return fail(SKML_E_ARG, "payload %d holds %lld values, the sum %lld", p, (long long)h[p].n, (long long)n);
-        if (h[p].num_bits != h[0].num_bits)
-            return fail(SKML_E_ARG, "payload %d has %d bits, payload 0 %d", p, h[p].num_bits, h[0].num_bits);
-        if (h[p].num_bits < kFxMinBits || h[p].num_bits > kFxMaxBits || h[p].words_offset != kFxHeaderBytes ||
-            skml_fixed_payload_bytes(n, h[p].num_bits) > stride)
-            return fail(SKML_E_ARG, "payload %d: inconsistent header or larger than the stride %zu", p, stride);
-    }
+    int bits = 0;
+    if (const int st = fixed_sum_headers(c, payloads, P, stride, n, &bits)) return st;
     KernelTimer kt(c, SKML_K_DECODE_SUM);
-    HIP_TRY(launch_fixed_decode_sum(c->stream, payloads, P, stride, out, n, scale, h[0].num_bits));
+    HIP_TRY(launch_fixed_decode_sum(c->stream, payloads, P, stride, out, n, scale, bits));
     return SKML_OK;
 }
 
@@ -121,3 +103,30 @@ int skml_fixed_info(skml_ctx* c, const void* payload, skml_fixed_header* hdr) {
 }
 
 }  // extern "C"
+
+int skml::fixed_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* bits) {
+    if (!c || !valid_payload_ptr(payloads) || stride % 256 || P < 1 || P > 16 || n < 1)
+        return fail(SKML_E_ARG, "bad decode_sum arguments (P in [1,16], 256-B aligned payloads)");
+    HIP_TRY(hipSetDevice(c->device));
+    // the headers come back through the context's pinned staging, as in dense_sum_headers
+    skml_fixed_header* h = static_cast<skml_fixed_header*>(skml::ctx_pinned(c, sizeof(skml_fixed_header) * 16));
+    if (!h) return fail(SKML_E_OOM, "pinned staging of the payload headers");
+    for (int p = 0; p < P; p++)
+        HIP_TRY(hipMemcpyAsync(h + p, static_cast<const char*>(payloads) + (size_t)p * stride, sizeof(skml_fixed_header),
+                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int p = 0; p < P; p++) {
+        if (h[p].magic != SKML_FIXED_MAGIC) return fail(SKML_E_STATE, "payload %d is not a fixed-point payload", p);
+        if (h[p].status == SKML_E_NAN) return fail(SKML_E_NAN, "payload %d: NaN, infinite or underflowed input", p);
+        if (h[p].status != SKML_OK) return fail(SKML_E_STATE, "payload %d has status %d", p, h[p].status);
+        if (h[p].n != n)
+            return fail(SKML_E_ARG, "payload %d holds %lld values, the sum %lld", p, (long long)h[p].n, (long long)n);
+        if (h[p].num_bits != h[0].num_bits)
+            return fail(SKML_E_ARG, "payload %d has %d bits, payload 0 %d", p, h[p].num_bits, h[0].num_bits);
+        if (h[p].num_bits < kFxMinBits || h[p].num_bits > kFxMaxBits || h[p].words_offset != kFxHeaderBytes ||
+            skml_fixed_payload_bytes(n, h[p].num_bits) > stride)
+            return fail(SKML_E_ARG, "payload %d: inconsistent header or larger than the stride %zu", p, stride);
+    }
+    *bits = h[0].num_bits;
+    return SKML_OK;
+}

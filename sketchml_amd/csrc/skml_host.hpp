@@ -160,4 +160,9 @@ int ensure_ws(skml_ctx* ctx, int64_t chunks, Workspace* w);
 int dense_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* common_bits,
                       int* max_bins);
 
+// The same for P gathered fixed-point payloads (skml_fixed_decode_sum_f32, the fused fixed-point
+// optimiser step; skml_fixed_api.cpp): magic, status (SKML_E_NAN), n, one num_bits, stride.
+// *bits: the payloads' width.
+int fixed_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* bits);
+
 }  // namespace skml

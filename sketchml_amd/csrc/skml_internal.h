@@ -242,6 +242,12 @@ hipError_t launch_opt_count(hipStream_t st, const void* g, int g_wide, int64_t n
 // keys strictly increasing (not verified; a key outside [0, dim) is skipped)
 hipError_t launch_opt_step_kv(hipStream_t st, const int32_t* keys, const void* vals, int v_wide, int64_t nnz,
                               int64_t dim, double scale, const OptConsts& k, int wide, void* w, void* m, void* v);
+// launch_decode_sum_step and launch_decode_sum_live for P fixed-point payloads of one width `bits`
+// (skml_fixed.hip): k_fixed_decode_sum's walk with the update, or the count, in place of the store.
+hipError_t launch_fixed_decode_sum_step(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n,
+                                        double scale, int bits, const OptConsts& k, int wide, void* w, void* m, void* v);
+hipError_t launch_fixed_decode_sum_live(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n,
+                                        double scale, int bits, unsigned long long* count);
 // ---- ZipMLQuantizer (skml_zip.hip) ----
 constexpr int kZipMinBins = 4;   // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
 constexpr int kZipTail = 4096;   // splitNum at which the rounds move into one workgroup's LDS

@@ -5,107 +5,14 @@
 //   k_decode_sum_step_gen  the same for > 8 payloads, mixed code widths and tables beyond the LDS bound
 //   k_decode_sum_live      #{|g| > 1e-8} of the same sum (toAuto's count)
 //   k_opt_step / k_opt_count / k_opt_step_kv   the update from a dense array and from keys + values
-// One __device__ function (opt_apply) holds the arithmetic; every form calls it.
+// One __device__ function (opt_apply, skml_opt.hpp) holds the arithmetic; every form calls it.
 #include <algorithm>
 
 #include "skml_codes.hpp"
 #include "skml_device.hpp"
+#include "skml_opt.hpp"
 
 namespace skml {
-
-typedef float of32x4 __attribute__((ext_vector_type(4)));
-typedef double of64x2 __attribute__((ext_vector_type(2)));
-
-// 8 consecutive values from / to p + e0 as 16-byte accesses (p 16-byte aligned, e0 a multiple of 8).
-template <typename T>
-__device__ __forceinline__ void load8(const T* __restrict__ p, int64_t e0, T (&x)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        const of32x4* s = reinterpret_cast<const of32x4*>(p + e0);
-        const of32x4 a = s[0], b = s[1];
-        x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-    } else {
-        const of64x2* s = reinterpret_cast<const of64x2*>(p + e0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const of64x2 a = s[j];
-            x[2 * j] = a.x; x[2 * j + 1] = a.y;
-        }
-    }
-}
-template <typename T>
-__device__ __forceinline__ void store8(T* __restrict__ p, int64_t e0, const T (&x)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        of32x4* d = reinterpret_cast<of32x4*>(p + e0);
-        d[0] = of32x4{x[0], x[1], x[2], x[3]};
-        d[1] = of32x4{x[4], x[5], x[6], x[7]};
-    } else {
-        of64x2* d = reinterpret_cast<of64x2*>(p + e0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) d[j] = of64x2{x[2 * j], x[2 * j + 1]};
-    }
-}
-
-// The update of one element, in double in the reference's operation order (Adam.scala:54-59,
-// GradientDescent.scala:108; the build has -ffp-contract=off, sqrt and / are correctly rounded).
-// fp32 state is widened on load; ng uses the unrounded m_t and v_t; each of w, m, v is rounded once,
-// at its store.  An element that the LIVE selection leaves out keeps its bits.
-template <bool ADAM, typename W>
-__device__ __forceinline__ void opt_apply(double g, W& w, W& m, W& v, const OptConsts& k) {
-    const bool upd = !k.live || fabs(g) > 1e-8;  // DenseDoubleGradient.toSparse's Math.abs(x) > Maths.EPS
-    if constexpr (ADAM) {
-        const double m_t = k.beta1 * (double)m + k.omb1 * g;
-        const double v_t = k.beta2 * (double)v + (k.omb2 * g) * g;
-        const double ng = (k.c_m * m_t) / (k.c_d * (sqrt(v_t) + k.eps));
-        const double w_t = (double)w - ng * k.lr;
-        w = upd ? (W)w_t : w;
-        m = upd ? (W)m_t : m;
-        v = upd ? (W)v_t : v;
-    } else {
-        const double w_t = (double)w - g * k.lr;
-        w = upd ? (W)w_t : w;
-    }
-}
-
-// A lane's 8 elements at e0: state in, update, state out.
-template <bool ADAM, typename W>
-struct State8 {
-    W w[8], m[8], v[8];
-    __device__ __forceinline__ void load(const W* __restrict__ pw, const W* __restrict__ pm, const W* __restrict__ pv,
-                                         int64_t e0) {
-        load8(pw, e0, w);
-        if constexpr (ADAM) {
-            load8(pm, e0, m);
-            load8(pv, e0, v);
-        }
-    }
-    __device__ __forceinline__ void apply(const double (&g)[8], const OptConsts& k) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) opt_apply<ADAM>(g[e], w[e], m[e], v[e], k);
-    }
-    __device__ __forceinline__ void store(W* __restrict__ pw, W* __restrict__ pm, W* __restrict__ pv, int64_t e0) {
-        store8(pw, e0, w);
-        if constexpr (ADAM) {
-            store8(pm, e0, m);
-            store8(pv, e0, v);
-        }
-    }
-};
-// One element (the last n % 8, and the key / value form).
-template <bool ADAM, typename W>
-__device__ __forceinline__ void opt_apply_at(double g, W* __restrict__ pw, W* __restrict__ pm, W* __restrict__ pv,
-                                             int64_t i, const OptConsts& k) {
-    W w = pw[i], m = W(0), v = W(0);
-    if constexpr (ADAM) {
-        m = pm[i];
-        v = pv[i];
-    }
-    opt_apply<ADAM>(g, w, m, v, k);
-    pw[i] = w;
-    if constexpr (ADAM) {
-        pm[i] = m;
-        pv[i] = v;
-    }
-}
 
 // Waves per SIMD asked of the fused form (a minimum: the register allocator's cap).  SGD on fp32
 // state adds 8 registers to the decode-sum's lane and keeps its values.  Adam holds 24 (fp32) or 48
@@ -152,7 +59,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<
         for (int q = 0; q < kOccMaxP; q++)
 #pragma unroll
             for (int j = 0; j < kW; j++) cw[q][j] = wn[q][j];
-        State8<ADAM, W> s;
+        StateN<ADAM, W, kOptPer> s;
         s.load(pw, pm, pv, g * kOptPer);
         if (g + gstep < full) {
 #pragma unroll
@@ -278,7 +185,7 @@ __global__ __launch_bounds__(256) void k_decode_sum_step_gen(const uint8_t* __re
     gen_fill(t, payloads, P, stride);
     const int64_t full = n / kOptPer, gstep = (int64_t)gridDim.x * 256;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < full; g += gstep) {
-        State8<ADAM, W> s;
+        StateN<ADAM, W, kOptPer> s;
         s.load(pw, pm, pv, g * kOptPer);
         double acc[kOptPer];
         gen_sum8(t, payloads, P, stride, g * kOptPer, acc);
@@ -292,20 +199,6 @@ __global__ __launch_bounds__(256) void k_decode_sum_step_gen(const uint8_t* __re
         if (e < n) opt_apply_at<ADAM>(gen_sum1(t, payloads, P, stride, e) * scale, pw, pm, pv, e, k);
     }
 }
-
-// A workgroup's live count into *count: a ballot and a popcount per wave and element slot, one LDS
-// add per wave, one global atomic per workgroup.  Every lane of a wave reaches every call.
-struct LiveCount {
-    unsigned long long wave = 0;  // wave-uniform
-    __device__ __forceinline__ void add(bool live) { wave += (unsigned long long)__popcll(__ballot(live)); }
-    __device__ __forceinline__ void finish(unsigned long long* s_cnt, unsigned long long* count) {
-        if (threadIdx.x == 0) *s_cnt = 0;
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0 && wave) atomicAdd(s_cnt, wave);
-        __syncthreads();
-        if (threadIdx.x == 0 && *s_cnt) atomicAdd(count, *s_cnt);
-    }
-};
 
 __global__ __launch_bounds__(256) void k_decode_sum_live(const uint8_t* __restrict__ payloads, int P, size_t stride,
                                                          int64_t n, double scale, unsigned long long* count) {
@@ -340,8 +233,8 @@ __global__ __launch_bounds__(256) void k_opt_step(const G* __restrict__ x, int64
     const int64_t full = n / kOptPer, gstep = (int64_t)gridDim.x * 256;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < full; g += gstep) {
         G xv[kOptPer];
-        load8(x, g * kOptPer, xv);
-        State8<ADAM, W> s;
+        load_state(x, g * kOptPer, xv);
+        StateN<ADAM, W, kOptPer> s;
         s.load(pw, pm, pv, g * kOptPer);
         double gr[kOptPer];
 #pragma unroll
@@ -365,7 +258,7 @@ __global__ __launch_bounds__(256) void k_opt_count(const G* __restrict__ x, int6
     for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x - lane); base < full; base += gstep) {
         const bool on = base + lane < full;
         G xv[kOptPer] = {};
-        if (on) load8(x, (base + lane) * kOptPer, xv);
+        if (on) load_state(x, (base + lane) * kOptPer, xv);
 #pragma unroll
         for (int e = 0; e < kOptPer; e++) lc.add(on && fabs((double)xv[e] * scale) > 1e-8);
     }

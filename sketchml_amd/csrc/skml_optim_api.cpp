@@ -109,6 +109,36 @@ int decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t strid
     return SKML_OK;
 }
 
+// The fixed-point twin of decode_sum_step_x.  The payloads end at the last one's own bytes, which
+// its header's width gives: what can be refused without the headers (a state range that reaches
+// into the narrowest payloads these could be) is refused before any device work, the rest once
+// fixed_sum_headers has read them back; nothing is launched before either.
+int fixed_decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, double scale,
+                            const skml_opt_params* p, int wide, void* w, void* m, void* v) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (n < 1 || n > 0x7FFFFFFFLL) return fail(SKML_E_ARG, "n=%lld outside [1, 2^31 - 1]", (long long)n);
+    if (P < 1 || P > 16) return fail(SKML_E_ARG, "P=%d outside [1, 16]", P);
+    const size_t sb = (size_t)n * (wide ? 8 : 4), before_last = (size_t)(P - 1) * stride;
+    Range r[4] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"},
+                  {payloads, before_last + skml_fixed_payload_bytes(n, kFxMinBits), "payloads"}};
+    if (const int st = check_common(c, p, r, 4)) return st;
+    int bits = 0;
+    if (const int st = fixed_sum_headers(c, payloads, P, stride, n, &bits)) return st;
+    r[3].bytes = before_last + skml_fixed_payload_bytes(n, bits);
+    for (int i = 0; i < 3; i++)
+        if (overlap(r[i], r[3])) return fail(SKML_E_ARG, "%s and %s overlap", r[i].name, r[3].name);
+    KernelTimer kt(c, SKML_K_DECODE_SUM);
+    int live = p->select == SKML_OPT_LIVE;
+    if (p->select == SKML_OPT_AUTO) {
+        unsigned long long* cnt = nullptr;
+        if (const int st = counter_zeroed(c, &cnt)) return st;
+        HIP_TRY(launch_fixed_decode_sum_live(c->stream, payloads, P, stride, n, scale, bits, cnt));
+        if (const int st = auto_choice(c, cnt, n, &live)) return st;
+    }
+    HIP_TRY(launch_fixed_decode_sum_step(c->stream, payloads, P, stride, n, scale, bits, consts_of(*p, live), wide, w, m, v));
+    return SKML_OK;
+}
+
 int opt_step_x(skml_ctx* c, const void* g, int32_t g_fp64, int64_t n, double scale, const skml_opt_params* p, int wide,
                void* w, void* m, void* v) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -172,6 +202,16 @@ int skml_dense_decode_sum_step_f32(skml_ctx* c, const void* payloads, int32_t P,
 int skml_dense_decode_sum_step_f64(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, double scale,
                                    const skml_opt_params* p, double* w, double* m, double* v) {
     return decode_sum_step_x(c, payloads, P, stride, n, scale, p, 1, w, m, v);
+}
+
+int skml_fixed_decode_sum_step_f32(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, double scale,
+                                   const skml_opt_params* p, float* w, float* m, float* v) {
+    return fixed_decode_sum_step_x(c, payloads, P, stride, n, scale, p, 0, w, m, v);
+}
+
+int skml_fixed_decode_sum_step_f64(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, double scale,
+                                   const skml_opt_params* p, double* w, double* m, double* v) {
+    return fixed_decode_sum_step_x(c, payloads, P, stride, n, scale, p, 1, w, m, v);
 }
 
 int skml_opt_step_f32(skml_ctx* c, const void* g, int32_t g_fp64, int64_t n, double scale, const skml_opt_params* p,

@@ -181,6 +181,17 @@ def decode_sum_fixed_point(ctx_handle, payloads: torch.Tensor, nranks: int, stri
                                              C.c_void_p(out.data_ptr()), n, float(scale)), "fixed_decode_sum")
 
 
+def decode_sum_update_fixed_point(ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, n: int, scale: float,
+                                  optimizer, weight: torch.Tensor, select: int = _lib.SKML_OPT_ALL) -> None:
+    """decode_sum_update for gathered FixedPointGradient payloads of one numBits and n
+    (skml_fixed_decode_sum_step_f32 / _f64): the sum of the decoded doubles, scaled, goes into the
+    update as the double it is, where decode_sum_fixed_point would round it to float."""
+    if int(n) != optimizer.dim:
+        raise SketchMLException(f"decode_sum_update_fixed_point: n={n}, the optimiser's dim is {optimizer.dim}")
+    optimizer._begin_update()
+    optimizer.step_fixed_payloads(ctx_handle, payloads, nranks, stride, scale, weight, select)
+
+
 # ---- one split table across ranks (SURVEY §8e single-split-table mode) ----------------------
 def parallel_slices(n_total: int, parts: int) -> list[int]:
     """Slice sizes of QuantileQuantizer.parallelQuantize (QuantileQuantizer.java:66-68): n/T

@@ -1,6 +1,6 @@
 """The optimiser update on the device: the reference's GradientDescent and Adam
 (ml/objective/GradientDescent.scala:16-21,89-117, ml/objective/Adam.scala:16-77) over the
-skml_opt_step_* / skml_dense_decode_sum_step_* entries of include/skml.h.
+skml_opt_step_* / skml_dense_decode_sum_step_* / skml_fixed_decode_sum_step_* entries of include/skml.h.
 
 The weight is a device tensor (float64 as the reference's DenseVector, or float32); Adam's m and
 v are tensors of the weight's dtype that the optimiser owns.  All arithmetic runs in double in the
@@ -91,7 +91,7 @@ class GradientDescent:
         else:
             raise SketchMLException(f"ClassNotFoundException: {kind}")
 
-    # ---- the three device forms; none of them advances beta_t ----
+    # ---- the device forms; none of them advances beta_t ----
     def step_array(self, values, weight: torch.Tensor, scale: float = 1.0, select: int = ALL) -> None:
         """skml_opt_step_*: g = scale * values (float32 or float64, in double)."""
         self._check_weight(weight)
@@ -129,6 +129,17 @@ class GradientDescent:
               else _lib.lib.skml_dense_decode_sum_step_f32)
         check(fn(ctx_handle, _ptr(payloads), int(nranks), int(stride), self.dim, float(scale), C.byref(p),
                  _ptr(weight), _ptr(m), _ptr(v)), "decode_sum_step")
+
+    def step_fixed_payloads(self, ctx_handle, payloads: torch.Tensor, nranks: int, stride: int, scale: float,
+                            weight: torch.Tensor, select: int = ALL) -> None:
+        """skml_fixed_decode_sum_step_*: the same for gathered FixedPointGradient payloads of one numBits."""
+        self._check_weight(weight)
+        m, v = self._state(weight)
+        p = self.params(select)
+        fn = (_lib.lib.skml_fixed_decode_sum_step_f64 if weight.dtype == torch.float64
+              else _lib.lib.skml_fixed_decode_sum_step_f32)
+        check(fn(ctx_handle, _ptr(payloads), int(nranks), int(stride), self.dim, float(scale), C.byref(p),
+                 _ptr(weight), _ptr(m), _ptr(v)), "fixed_decode_sum_step")
 
 
 class Adam(GradientDescent):

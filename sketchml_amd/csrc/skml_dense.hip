@@ -17,8 +17,15 @@ namespace skml {
 #ifndef SKML_Q_THREADS
 #define SKML_Q_THREADS 256
 #endif
-#ifndef SKML_Q_GRID
-#define SKML_Q_GRID 1024
+// Cap on the quantize pass's persistent grid.  fp32 input (HBM-bound): 1,024 workgroups, 4 on each
+// of the MI355X's 256 CUs; every resident workgroup (8 per CU with the byte table) measured slower.
+// 16-bit input (short of both limits at 4 waves per SIMD): every workgroup the runtime's occupancy
+// query reports resident.  SKML_Q_GRID (A/B builds): one cap for every input type, 0 for residency
+// (DESIGN section 10 item 5).
+#ifdef SKML_Q_GRID
+constexpr int kQGridF32 = SKML_Q_GRID, kQGridLowp = SKML_Q_GRID;
+#else
+constexpr int kQGridF32 = 1024, kQGridLowp = 0;
 #endif
 constexpr int kQThreads = SKML_Q_THREADS;
 constexpr int kEytzMax = 4096;
@@ -87,16 +94,17 @@ __device__ __forceinline__ void store_codes8(uint8_t* codes, int64_t e0, const u
 // build_quant_lut); NaN values take Quantizer.indexOf's NaN bin.
 constexpr int kModeEytz = 8, kModeGlobal = 9, kModeJava = 10;
 
+template <typename E>
 struct QuantTables {
-    const uint16_t* base;  // LDS bucket bases
+    const E* base;         // LDS bucket bases (bytes when the payload has at most 255 splits)
     const float* S;        // LDS splits (+NaN padding), or Eytzinger array
     const double* sp;      // payload splits (global / Java mode)
     int nsplit, levels, zero;
     uint32_t P, nan_bin;
 };
 
-template <int MODE>
-__device__ __forceinline__ uint32_t quant_bin(const QuantTables& q, float xv) {
+template <int MODE, typename E>
+__device__ __forceinline__ uint32_t quant_bin(const QuantTables<E>& q, float xv) {
     uint32_t bin;
     if constexpr (MODE <= 4) {
         bin = q.base[f2key(__float_as_uint(xv)) >> (32 - kLutBits)];
@@ -131,11 +139,21 @@ __device__ __forceinline__ uint32_t quant_bin(const QuantTables& q, float xv) {
 #define SKML_Q_STORE 0
 #endif
 constexpr int kQStageWords = 256;  // per wave: 1,024 one-byte codes
+// Tiles of loads a wave holds ahead of the one it bins (SKML_Q_DEPTH, A/B builds): 1 (default), or
+// 2 for twice the bytes in flight per wave at +16 VGPRs (fp32) / +8 (16-bit input).
+#ifndef SKML_Q_DEPTH
+#define SKML_Q_DEPTH 1
+#endif
+constexpr int kQDepth = SKML_Q_DEPTH;
+static_assert(kQDepth == 1 || kQDepth == 2, "one or two tiles in flight");
+// Waves per SIMD the kernel is compiled for: 8 (64 VGPRs) holds one tile ahead; two tiles ahead
+// need 6 (80 VGPRs), the fp32 form spills at 8.
+constexpr int kQWaves = kQDepth == 1 ? 8 : 6;
 
 // X: the storage type of x.  A 16-bit tile of 1,024 values is 2 KiB: two 16-byte loads (8 values
 // each) per lane, widened in registers; quant_bin sees the same floats as the fp32 form.
-template <int MODE, typename X = float>
-__device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __restrict__ x, int64_t n,
+template <int MODE, typename X = float, typename E = uint16_t>
+__device__ __forceinline__ void quant_tiles(const QuantTables<E>& q, const X* __restrict__ x, int64_t n,
                                             uint8_t* __restrict__ codes, int bits, uint32_t* __restrict__ stage) {
     const int lane = threadIdx.x & 63;
     const int64_t nwaves_total = (int64_t)gridDim.x * (kQThreads / 64);
@@ -143,19 +161,23 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
     const int64_t full_tiles = n / 1024;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     if constexpr (is_lowp<X>::value) {
-        // software-pipelined like the fp32 form: the next tile's 2 KiB is in flight while this one is binned
-        u32x4_v f[2];
-        if (wave_id < full_tiles) {
-            const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + wave_id * 1024);
+        // software-pipelined like the fp32 form: the next kQDepth tiles' 2 KiB each are in flight while
+        // this one is binned
+        u32x4_v f[kQDepth][2];
 #pragma unroll
-            for (int j = 0; j < 2; j++) f[j] = __builtin_nontemporal_load(src + j * 64 + lane);
+        for (int d = 0; d < kQDepth; d++) {
+            if (wave_id + d * nwaves_total < full_tiles) {
+                const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + (wave_id + d * nwaves_total) * 1024);
+#pragma unroll
+                for (int j = 0; j < 2; j++) f[d][j] = __builtin_nontemporal_load(src + j * 64 + lane);
+            }
         }
         const bool wt = SKML_Q_STORE != 0 && bits == 8 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0;
         const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
             codes, 0, (int)std::min<int64_t>(full_tiles * 1024, (int64_t)0x7FFFFC00), 0x00020000);
         for (int64_t tile = wave_id; tile < full_tiles; tile += nwaves_total) {
             u32x4_v g[2];
-            const int64_t next = tile + nwaves_total;
+            const int64_t next = tile + kQDepth * nwaves_total;
             if (next < full_tiles) {
                 const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + next * 1024);
 #pragma unroll
@@ -164,7 +186,7 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 float v[8];
-                widen8<X>(f[j], v);
+                widen8<X>(f[0][j], v);
                 uint32_t c[8];
 #pragma unroll
                 for (int e = 0; e < 8; e++) c[e] = quant_bin<MODE>(q, v[e]);
@@ -183,15 +205,22 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
                                                        SKML_Q_STORE == 2 ? 16 /* sc1: write-through */ : 2 /* nt */);
             }
 #pragma unroll
-            for (int j = 0; j < 2; j++) f[j] = g[j];
+            for (int j = 0; j < 2; j++) {
+#pragma unroll
+                for (int d = 0; d + 1 < kQDepth; d++) f[d][j] = f[d + 1][j];
+                f[kQDepth - 1][j] = g[j];
+            }
         }
     } else {
-    // software-pipelined: the next tile's 4 KiB is in flight while this one is binned
-    f32x4 f[4];
-    if (wave_id < full_tiles) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(x + wave_id * 1024);
+    // software-pipelined: the next kQDepth tiles' 4 KiB each are in flight while this one is binned
+    f32x4 f[kQDepth][4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) f[j] = __builtin_nontemporal_load(src + j * 64 + lane);
+    for (int d = 0; d < kQDepth; d++) {
+        if (wave_id + d * nwaves_total < full_tiles) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(x + (wave_id + d * nwaves_total) * 1024);
+#pragma unroll
+            for (int j = 0; j < 4; j++) f[d][j] = __builtin_nontemporal_load(src + j * 64 + lane);
+        }
     }
     // codes are < 4 GB past `codes` (n < 2^31): one buffer descriptor, 32-bit offsets
     const bool wt = SKML_Q_STORE != 0 && bits == 8 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0;
@@ -199,7 +228,7 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
         codes, 0, (int)std::min<int64_t>(full_tiles * 1024, (int64_t)0x7FFFFC00), 0x00020000);
     for (int64_t tile = wave_id; tile < full_tiles; tile += nwaves_total) {
         f32x4 g[4];
-        const int64_t next = tile + nwaves_total;
+        const int64_t next = tile + kQDepth * nwaves_total;
         if (next < full_tiles) {
             const f32x4* src = reinterpret_cast<const f32x4*>(x + next * 1024);
 #pragma unroll
@@ -208,8 +237,8 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
         if (wt) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const uint32_t c0 = quant_bin<MODE>(q, f[j].x), c1 = quant_bin<MODE>(q, f[j].y);
-                const uint32_t c2 = quant_bin<MODE>(q, f[j].z), c3 = quant_bin<MODE>(q, f[j].w);
+                const uint32_t c0 = quant_bin<MODE>(q, f[0][j].x), c1 = quant_bin<MODE>(q, f[0][j].y);
+                const uint32_t c2 = quant_bin<MODE>(q, f[0][j].z), c3 = quant_bin<MODE>(q, f[0][j].w);
                 stage[j * 64 + lane] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
             }
             __builtin_amdgcn_wave_barrier();
@@ -221,13 +250,17 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
         } else {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const uint32_t c0 = quant_bin<MODE>(q, f[j].x), c1 = quant_bin<MODE>(q, f[j].y);
-                const uint32_t c2 = quant_bin<MODE>(q, f[j].z), c3 = quant_bin<MODE>(q, f[j].w);
+                const uint32_t c0 = quant_bin<MODE>(q, f[0][j].x), c1 = quant_bin<MODE>(q, f[0][j].y);
+                const uint32_t c2 = quant_bin<MODE>(q, f[0][j].z), c3 = quant_bin<MODE>(q, f[0][j].w);
                 store_codes4(codes, tile * 1024 + j * 256 + lane * 4, c0, c1, c2, c3, bits, lane);
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; j++) f[j] = g[j];
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int d = 0; d + 1 < kQDepth; d++) f[d][j] = f[d + 1][j];
+            f[kQDepth - 1][j] = g[j];
+        }
     }
     }
     // tail tile (n % 1024 values), one wave, guarded element loads
@@ -251,20 +284,30 @@ __device__ __forceinline__ void quant_tiles(const QuantTables& q, const X* __res
     }
 }
 
-// Dynamic LDS: [0, 32 KB) bucket bases, then `lds_splits` floats (LUT mode); Eytzinger mode
-// reuses the start of the same buffer (P <= 4096 floats).
-template <typename X = float>
-__global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_quantize(const X* __restrict__ x, int64_t n,
+// Dynamic LDS: [0, kLutSize entries of E) bucket bases, then `lds_splits` floats (LUT mode);
+// Eytzinger mode reuses the start of the same buffer (P <= 4096 floats, 16 KB: the byte table's size).
+// E: the bucket entry, uint8_t when the payload has at most 255 splits (the host chooses it from the
+// requested bins), uint16_t otherwise.  lut == nullptr: the workgroup builds the bucket table itself
+// from the payload's splits (build_quant_lut on its own LDS: the table is a pure function of them);
+// otherwise (E = uint16_t) it copies the caller's table, whose cmax may also ask for kModeJava.
+template <typename X = float, typename E = uint16_t>
+__global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(kQWaves))) void k_quantize(const X* __restrict__ x, int64_t n,
                                                         uint8_t* __restrict__ payload,
                                                         const QuantLut* __restrict__ lut, int lds_splits) {
     extern __shared__ __align__(16) uint8_t qsm[];
+    __shared__ int q_misc[20];
+#if SKML_Q_STORE != 0
     __shared__ __align__(16) uint32_t qstage[kQThreads / 64][kQStageWords];
+    uint32_t* stage = qstage[threadIdx.x >> 6];
+#else
+    uint32_t* stage = nullptr;  // the default store form stages nothing: no LDS for it
+#endif
     const skml_dense_header* hdr = reinterpret_cast<const skml_dense_header*>(payload);
     if (hdr->status != SKML_OK) return;
     const int bins = hdr->bin_num, bits = hdr->code_bits, nsplit = bins - 1;
     const double* sp = reinterpret_cast<const double*>(payload + kHeaderBytes);
     uint8_t* codes = payload + hdr->codes_offset;
-    QuantTables q;
+    QuantTables<E> q;
     q.sp = sp;
     q.nsplit = nsplit;
     q.nan_bin = (uint32_t)nan_bin_for(bins, hdr->zero_idx);
@@ -275,43 +318,60 @@ __global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(8))) 
         q.P <<= 1;
         q.levels++;
     }
-    const int cmax = lut ? lut->cmax : -1;
+    constexpr size_t kBaseBytes = (size_t)kLutSize * sizeof(E);
+    constexpr int kMaxEntry = sizeof(E) == 1 ? 255 : kLutMaxSplits;  // base[b] <= nsplit must fit E
+    E* base = reinterpret_cast<E*>(qsm);
+    float* S = reinterpret_cast<float*>(qsm + kBaseBytes);
+    const bool fits = nsplit + kLutPad <= lds_splits && nsplit <= kMaxEntry;
+    int cmax = -1;
+    if (lut) {
+        if constexpr (sizeof(E) == 2) cmax = lut->cmax;
+    } else if (fits) {
+        cmax = 0;  // decided by the build below
+    }
+    if (cmax >= 0 && fits) {
+        for (int i = threadIdx.x; i < nsplit + kLutPad; i += kQThreads)
+            S[i] = i < nsplit ? __double2float_ru(sp[i]) : __uint_as_float(0x7FC00000u);
+        if (lut) {
+            if constexpr (sizeof(E) == 2) {
+                const uint4* src = reinterpret_cast<const uint4*>(lut->base);
+                for (int i = threadIdx.x; i < (int)(kBaseBytes / 16); i += kQThreads)
+                    reinterpret_cast<uint4*>(base)[i] = src[i];
+            }
+        } else {
+            __syncthreads();  // S is the build's input
+            cmax = build_quant_lut<E>(S, nsplit, nullptr, q_misc, reinterpret_cast<uint32_t*>(base));
+        }
+    }
     int mode;
     if (cmax == kLutJavaMode) {
         mode = kModeJava;
-    } else if (cmax >= 0 && nsplit + kLutPad <= lds_splits) {
+    } else if (cmax >= 0 && fits) {
         mode = cmax == 0 ? 0 : 32 - __clz((uint32_t)cmax);  // bisection steps: ceil(log2(cmax+1))
-        uint16_t* base = reinterpret_cast<uint16_t*>(qsm);
-        float* S = reinterpret_cast<float*>(qsm + sizeof(lut->base));
-        const uint4* src = reinterpret_cast<const uint4*>(lut->base);
-        for (int i = threadIdx.x; i < (int)(sizeof(lut->base) / 16); i += kQThreads)
-            reinterpret_cast<uint4*>(base)[i] = src[i];
-        for (int i = threadIdx.x; i < nsplit + kLutPad; i += kQThreads)
-            S[i] = i < nsplit ? __double2float_ru(sp[i]) : __uint_as_float(0x7FC00000u);
         q.base = base;
         q.S = S;
     } else if (q.P <= kEytzMax) {
-        mode = kModeEytz;
-        float* E = reinterpret_cast<float*>(qsm);
+        mode = kModeEytz;  // (after a build that found cmax > kLutMaxNeed: over the table it left)
+        float* Ey = reinterpret_cast<float*>(qsm);
         for (uint32_t i = threadIdx.x + 1; i < q.P; i += kQThreads) {
             const int d = 31 - __clz(i);
             const uint32_t idx = ((2u * (i - (1u << d)) + 1u) << (q.levels - 1 - d)) - 1u;
-            E[i] = idx < (uint32_t)nsplit ? __double2float_ru(sp[idx]) : __uint_as_float(0x7FC00000u);
+            Ey[i] = idx < (uint32_t)nsplit ? __double2float_ru(sp[idx]) : __uint_as_float(0x7FC00000u);
         }
-        q.S = E;
+        q.S = Ey;
     } else {
         mode = kModeGlobal;
     }
     __syncthreads();
     switch (mode) {
-        case 0: quant_tiles<0>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case 1: quant_tiles<1>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case 2: quant_tiles<2>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case 3: quant_tiles<3>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case 4: quant_tiles<4>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case kModeEytz: quant_tiles<kModeEytz>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        case kModeJava: quant_tiles<kModeJava>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
-        default: quant_tiles<kModeGlobal>(q, x, n, codes, bits, qstage[threadIdx.x >> 6]); break;
+        case 0: quant_tiles<0>(q, x, n, codes, bits, stage); break;
+        case 1: quant_tiles<1>(q, x, n, codes, bits, stage); break;
+        case 2: quant_tiles<2>(q, x, n, codes, bits, stage); break;
+        case 3: quant_tiles<3>(q, x, n, codes, bits, stage); break;
+        case 4: quant_tiles<4>(q, x, n, codes, bits, stage); break;
+        case kModeEytz: quant_tiles<kModeEytz>(q, x, n, codes, bits, stage); break;
+        case kModeJava: quant_tiles<kModeJava>(q, x, n, codes, bits, stage); break;
+        default: quant_tiles<kModeGlobal>(q, x, n, codes, bits, stage); break;
     }
 }
 
@@ -323,31 +383,80 @@ static int quant_grid(int64_t n) {
     return (int)wg;
 }
 
-hipError_t launch_quantize(hipStream_t st, const void* x, int64_t n, void* payload, const QuantLut* lut,
-                           int req_bins, int xtype) {
-    if (n <= 0) return hipSuccess;
-    // LDS sized for this request's split table; persistent-style grid (the LUT is loaded once per WG)
-    const int lds_splits = std::min(std::max(req_bins - 1, 1), kLutMaxSplits) + kLutPad;
-    const size_t lds = sizeof(QuantLut::base) + (size_t)lds_splits * sizeof(float);
+// Resident workgroups per CU of instantiation `inst` (3 * byte_table + xtype) with `lds` bytes of
+// dynamic LDS, as the runtime's occupancy query reports them; asked once per (inst, lds) and context.
+template <typename K>
+static hipError_t quant_residency(QuantResidency* res, int inst, size_t lds, K kernel, int* wgs) {
+    for (int i = 0; i < res->used; i++)
+        if (res->e[i].inst == inst && res->e[i].lds == lds) {
+            *wgs = res->e[i].wgs;
+            return hipSuccess;
+        }
+    if (res->cus == 0) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&res->cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+    }
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kQThreads, lds);
+    if (e != hipSuccess) return e;
+    if (nb < 1) return hipErrorInvalidConfiguration;
+    const int slot = res->used < QuantResidency::kSlots ? res->used++ : (res->next++ % QuantResidency::kSlots);
+    res->e[slot] = {inst, lds, nb};
+    *wgs = nb;
+    return hipSuccess;
+}
+
+template <typename X, typename E>
+static hipError_t launch_quantize_as(hipStream_t st, QuantResidency* res, int inst, const X* x, int64_t n, uint8_t* pl,
+                                     const QuantLut* lut, int lds_splits, int* wgs_out) {
+    const size_t lds = (size_t)kLutSize * sizeof(E) + (size_t)lds_splits * sizeof(float);
+    constexpr int kCap = is_lowp<X>::value ? kQGridLowp : kQGridF32;
+    int wgs = 0;
+    if (wgs_out || kCap == 0)
+        if (const hipError_t e = quant_residency(res, inst, lds, k_quantize<X, E>, &wgs)) return e;
+    if (wgs_out) {
+        *wgs_out = wgs;
+        return hipSuccess;
+    }
+    // persistent grid (the table is built or loaded once per workgroup), at least 4 tiles each
+    const int64_t cap = kCap > 0 ? (int64_t)kCap : (int64_t)res->cus * wgs;
     const int64_t tiles = (n + 1023) / 1024;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, SKML_Q_GRID));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, cap));
+    hipLaunchKernelGGL((k_quantize<X, E>), dim3(grid), dim3(kQThreads), lds, st, x, n, pl, lut, lds_splits);
+    return hipGetLastError();
+}
+
+// wgs_out (debug): report the resident workgroups per CU of the form these arguments select
+// instead of launching it.
+hipError_t launch_quantize(hipStream_t st, QuantResidency* res, const void* x, int64_t n, void* payload,
+                           const QuantLut* lut, int req_bins, int xtype, int* wgs_out) {
+    if (n <= 0 && !wgs_out) return hipSuccess;
+    // LDS sized for this request's split table.  A self-built table has byte entries when the
+    // request allows at most 255 splits; a passed table is the caller's 16-bit one.
+    const int lds_splits = std::min(std::max(req_bins - 1, 1), kLutMaxSplits) + kLutPad;
+    const bool bytes = !lut && req_bins <= 256;
     uint8_t* pl = reinterpret_cast<uint8_t*>(payload);
+    const int inst = 3 * (int)bytes + xtype;
     switch (xtype) {
-        case kXF32:
-            hipLaunchKernelGGL(k_quantize<float>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const float*>(x), n, pl,
-                               lut, lds_splits);
-            break;
-        case kXBF16:
-            hipLaunchKernelGGL(k_quantize<bf16_t>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const bf16_t*>(x), n,
-                               pl, lut, lds_splits);
-            break;
-        case kXF16:
-            hipLaunchKernelGGL(k_quantize<f16_t>, dim3(grid), dim3(kQThreads), lds, st, static_cast<const f16_t*>(x), n, pl,
-                               lut, lds_splits);
-            break;
+        case kXF32: {
+            const float* xf = static_cast<const float*>(x);
+            return bytes ? launch_quantize_as<float, uint8_t>(st, res, inst, xf, n, pl, lut, lds_splits, wgs_out)
+                         : launch_quantize_as<float, uint16_t>(st, res, inst, xf, n, pl, lut, lds_splits, wgs_out);
+        }
+        case kXBF16: {
+            const bf16_t* xb = static_cast<const bf16_t*>(x);
+            return bytes ? launch_quantize_as<bf16_t, uint8_t>(st, res, inst, xb, n, pl, lut, lds_splits, wgs_out)
+                         : launch_quantize_as<bf16_t, uint16_t>(st, res, inst, xb, n, pl, lut, lds_splits, wgs_out);
+        }
+        case kXF16: {
+            const f16_t* xh = static_cast<const f16_t*>(x);
+            return bytes ? launch_quantize_as<f16_t, uint8_t>(st, res, inst, xh, n, pl, lut, lds_splits, wgs_out)
+                         : launch_quantize_as<f16_t, uint16_t>(st, res, inst, xh, n, pl, lut, lds_splits, wgs_out);
+        }
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 // =============================================================================================

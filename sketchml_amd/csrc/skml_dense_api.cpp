@@ -262,7 +262,7 @@ int run_sketch_f32(skml_ctx* c, const void* x, int64_t n, uint64_t s0, const Wor
             KernelTimer kt(c, SKML_K_MERGE);
             HIP_TRY(launch_merge_pass(c->stream, passes[i], fuse_next ? &passes[i + 1] : nullptr, src, dst, next_dst,
                                       w.roots, s0, c->jump_tab, w.done, x, n, w.part, nwg, ranks_of(c), p->bin_num,
-                                      p->dedup ? 1 : 0, payload, w.raw, w.lut, w.ubits,
+                                      p->dedup ? 1 : 0, payload, w.raw, summary_lut(w.lut), w.ubits,
                                       summary ? w.part_red : nullptr, summary ? nred : 0, summary ? part_from : 0,
                                       xtype));
             src = dst;
@@ -314,11 +314,11 @@ static int dense_encode_x(skml_ctx* c, const void* x, int xtype, int64_t n, cons
     if (!fused) {
         KernelTimer kt(c, SKML_K_SUMMARY);
         HIP_TRY(launch_summary(c->stream, x, n, w.part, nwg, w.roots, ranks_of(c), p->bin_num,
-                               p->dedup ? 1 : 0, payload, w.raw, w.lut, xtype));
+                               p->dedup ? 1 : 0, payload, w.raw, summary_lut(w.lut), xtype));
     }
     {
         KernelTimer kt(c, SKML_K_QUANTIZE);
-        HIP_TRY(launch_quantize(c->stream, x, n, payload, w.lut, p->bin_num, xtype));
+        HIP_TRY(launch_quantize(c->stream, &c->qres, x, n, payload, summary_lut(w.lut), p->bin_num, xtype));
     }
     return SKML_OK;
 }
@@ -379,7 +379,7 @@ template <> struct SketchT<float> {
     using Ws = Workspace;
     static int ws(skml_ctx* c, int64_t chunks, Ws* w) { return ensure_ws(c, chunks, w); }
     static int lut(skml_ctx*, const Ws& w, QuantLut** lut) {
-        *lut = w.lut;
+        *lut = summary_lut(w.lut);  // none: the quantize pass builds its own table
         return SKML_OK;
     }
     static int sketch(skml_ctx* c, const float* x, int64_t n, uint64_t s0, const Ws& w) {
@@ -401,9 +401,9 @@ template <> struct SketchT<float> {
     static hipError_t uniform(hipStream_t st, const float* x, int64_t n, int bins, const Workspace& w, void* payload) {
         return launch_uniform(st, x, n, bins, w.uni, payload, w.lut, w.qflags);
     }
-    static hipError_t quantize(hipStream_t st, const float* x, int64_t n, void* payload, const QuantLut* lut,
+    static hipError_t quantize(skml_ctx* c, const float* x, int64_t n, void* payload, const QuantLut* lut,
                                const int*, int bins) {
-        return launch_quantize(st, x, n, payload, lut, bins);
+        return launch_quantize(c->stream, &c->qres, x, n, payload, lut, bins);
     }
 };
 template <> struct SketchT<double> {
@@ -434,9 +434,9 @@ template <> struct SketchT<double> {
     static hipError_t uniform(hipStream_t st, const double* x, int64_t n, int bins, const Workspace& w, void* payload) {
         return launch_uniform64(st, x, n, bins, w.uni, payload, w.lut, w.qflags);
     }
-    static hipError_t quantize(hipStream_t st, const double* x, int64_t n, void* payload, const QuantLut* lut,
+    static hipError_t quantize(skml_ctx* c, const double* x, int64_t n, void* payload, const QuantLut* lut,
                                const int* qflags, int bins) {
-        return launch_quantize64(st, x, n, payload, lut, qflags, bins);
+        return launch_quantize64(c->stream, x, n, payload, lut, qflags, bins);
     }
 };
 
@@ -520,7 +520,7 @@ int merge_and_quantize(skml_ctx* c, const T* x, int64_t n, const typename Sketch
                                           sk.tail, sk.part));
     }
     KernelTimer kt(c, SKML_K_QUANTIZE);
-    HIP_TRY(SketchT<T>::quantize(c->stream, x, n, payload, lut, nullptr, p->bin_num));
+    HIP_TRY(SketchT<T>::quantize(c, x, n, payload, lut, nullptr, p->bin_num));
     return SKML_OK;
 }
 
@@ -597,7 +597,7 @@ int encode_uniform(skml_ctx* c, const T* x, int64_t n, const skml_params* p, voi
     }
     {
         KernelTimer kt(c, SKML_K_QUANTIZE);
-        HIP_TRY(SketchT<T>::quantize(c->stream, x, n, payload, w.lut, w.qflags, p->bin_num));
+        HIP_TRY(SketchT<T>::quantize(c, x, n, payload, w.lut, w.qflags, p->bin_num));
     }
     return SKML_OK;
 }
@@ -714,8 +714,26 @@ int skml_dense_encode_with_splits_f32(skml_ctx* c, const float* x, int64_t n, co
     if ((st = ensure_ws(c, 0, &w))) return st;
     HIP_TRY(launch_set_splits(c->stream, payload, n, (const double*)c->stage.p, nsplits, mn, mx, nsplits + 1,
                               w.lut));
-    HIP_TRY(launch_quantize(c->stream, x, n, payload, w.lut, nsplits + 1));
+    HIP_TRY(launch_quantize(c->stream, &c->qres, x, n, payload, w.lut, nsplits + 1));
     HIP_TRY(hipStreamSynchronize(c->stream));  // the staged splits are reused by later calls
+    return SKML_OK;
+}
+
+// Profiling hook, not in include/skml.h (like skml_debug_prof): the resident workgroups per CU of
+// the quantize pass, as the runtime's occupancy query reports them for the kernel form that (xtype,
+// req_bins, passed_table: non-zero for the set-splits / uniform / ZipML encodes) selects, and the
+// device's CU count; their product caps the pass's grid.  Launches nothing.
+int skml_debug_quantize_residency(skml_ctx* c, int32_t xtype, int32_t req_bins, int32_t passed_table,
+                                  int32_t* wgs_per_cu, int32_t* cus) {
+    if (!c || !wgs_per_cu || !cus || req_bins < 2) return fail(SKML_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    Workspace w;
+    if (int st = ensure_ws(c, 0, &w)) return st;
+    int wgs = 0;
+    HIP_TRY(launch_quantize(c->stream, &c->qres, nullptr, 0, nullptr, passed_table ? w.lut : nullptr, req_bins, xtype,
+                            &wgs));
+    *wgs_per_cu = wgs;
+    *cus = c->qres.cus;
     return SKML_OK;
 }
 

@@ -742,66 +742,87 @@ __device__ __forceinline__ uint32_t lut_bucket_of(float f) {
     return f2key(u) >> (32 - kLutBits);
 }
 
-// s_misc: 20 ints of LDS; lbuf: kLutSize / 2 uint32 of LDS (u16 counts, then u16 bases in place).
-__device__ __forceinline__ void build_quant_lut(const float* sp, int nsplit, QuantLut* lut, int* s_misc,
-                                                uint32_t* lbuf, unsigned long long* prof = nullptr) {
-    const int T = blockDim.x, t = threadIdx.x, lane = t & 63, w = t >> 6, nw = T >> 6;
+// s_misc: 20 ints of LDS; lbuf: kLutSize entries of E in LDS (counts, then bases in place).
+// E = uint16_t: any split count up to kLutMaxSplits.  E = uint8_t: nsplit <= 255, so neither a
+// count nor a base leaves its byte (the packed 32-bit atomics cannot carry).
+// lut (E = uint16_t only, may be null): the global copy for a later quantize launch; with null
+// the table stays in lbuf for the calling workgroup.  Returns the table's cmax (-1: unusable) to
+// every thread; lbuf is complete on return.
+template <typename E = uint16_t>
+__device__ __forceinline__ int build_quant_lut(const float* sp, int nsplit, QuantLut* lut, int* s_misc,
+                                               uint32_t* lbuf, unsigned long long* prof = nullptr) {
+    static_assert(sizeof(E) == 1 || sizeof(E) == 2, "bucket entries are bytes or 16-bit words");
+    constexpr int kPerWord = 4 / (int)sizeof(E), kEntryBits = 8 * (int)sizeof(E);
+    constexpr int kPer16 = 16 / (int)sizeof(E);  // entries per 16-byte LDS access
+    constexpr uint32_t kEntryMask = (1u << kEntryBits) - 1u;
+    const int T = blockDim.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
     constexpr uint32_t kNegZeroBucket = 0x7FFFFFFFu >> (32 - kLutBits);
-    uint16_t* cnt = reinterpret_cast<uint16_t*>(lbuf);
-    for (int i = t; i < kLutSize / 2; i += T) lbuf[i] = 0u;
+    E* cnt = reinterpret_cast<E*>(lbuf);
+    for (int i = t; i < kLutSize / kPerWord; i += T) lbuf[i] = 0u;
     if (t < 20) s_misc[t] = 0;
     __syncthreads();
-    for (int i = t; i < nsplit; i += T) {  // histogram (u16 halves of u32 words)
+    for (int i = t; i < nsplit; i += T) {  // histogram (entries packed in u32 words)
         const uint32_t b = lut_bucket_of(sp[i]);
-        atomicAdd(&lbuf[b >> 1], 1u << (16 * (b & 1)));
+        atomicAdd(&lbuf[b / kPerWord], 1u << (kEntryBits * (b % kPerWord)));
         if ((__float_as_uint(sp[i]) & 0x7FFFFFFFu) == 0u) atomicAdd(&s_misc[0], 1);
     }
     __syncthreads();
     if (prof && t == 0) prof[0] = wall_clock64();  // profiling builds: histogram done
     // exclusive scan: each thread owns kLutSize / T consecutive buckets
-    const int per = kLutSize / T, b0 = t * per;  // per >= 16, a multiple of 8
+    const int per = kLutSize / T, b0 = t * per;  // per >= 16, a multiple of 16
     const uint4* c4 = reinterpret_cast<const uint4*>(cnt + b0);
     int sum = 0, cmax = 0;
-    for (int k = 0; k < per / 8; k++) {  // 8 u16 counts per 16-byte LDS read
+    for (int k = 0; k < per / kPer16; k++) {
         const uint4 q = c4[k];
         const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-            const int lo = (int)(wds[e] & 0xFFFFu), hi = (int)(wds[e] >> 16);
-            sum += lo + hi;
-            cmax = max(cmax, max(lo, hi));
+#pragma unroll
+            for (int h = 0; h < kPerWord; h++) {
+                const int c = (int)((wds[e] >> (kEntryBits * h)) & kEntryMask);
+                sum += c;
+                cmax = max(cmax, c);
+            }
         }
     }
-    if (b0 <= (int)kNegZeroBucket && (int)kNegZeroBucket < b0 + per) cmax = max(cmax, cnt[kNegZeroBucket] + s_misc[0]);
+    if (b0 <= (int)kNegZeroBucket && (int)kNegZeroBucket < b0 + per) cmax = max(cmax, (int)cnt[kNegZeroBucket] + s_misc[0]);
     const int inc = (int)wave_incl_scan_u32((uint32_t)sum);
     if (lane == 63) s_misc[4 + w] = inc;
     // one LDS atomic per wave (512 same-address atomics serialise: ~2 us)
     cmax = (int)wave_reduce_u32_lane63<1>((uint32_t)cmax);  // counts are >= 0
     if (lane == 63) atomicMax(&s_misc[1], cmax);
     __syncthreads();
-    int run = inc - sum;
+    int run = inc - sum;  // the carry into this thread: splits in the buckets of the threads before it
     for (int j = 0; j < w; j++) run += s_misc[4 + j];
-    (void)nw;
     uint4* o4 = reinterpret_cast<uint4*>(cnt + b0);
-    for (int k = 0; k < per / 8; k++) {  // counts -> bases in place, 8 per 16-byte access
+    for (int k = 0; k < per / kPer16; k++) {  // counts -> bases in place
         const uint4 q = o4[k];
         uint32_t wds[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-            const uint32_t lo = wds[e] & 0xFFFFu, hi = wds[e] >> 16;
-            const uint32_t blo = (uint32_t)run;
-            run += (int)lo;
-            wds[e] = blo | ((uint32_t)run << 16);
-            run += (int)hi;
+            uint32_t out = 0u;
+#pragma unroll
+            for (int h = 0; h < kPerWord; h++) {
+                out |= (uint32_t)run << (kEntryBits * h);
+                run += (int)((wds[e] >> (kEntryBits * h)) & kEntryMask);
+            }
+            wds[e] = out;
         }
         o4[k] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
     }
     __syncthreads();
     if (prof && t == 0) prof[1] = wall_clock64();  // profiling builds: scan done
-    const uint4* src = reinterpret_cast<const uint4*>(lbuf);
-    uint4* dst = reinterpret_cast<uint4*>(lut->base);
-    for (int i = t; i < (int)(sizeof(lut->base) / (sizeof(uint4))); i += T) dst[i] = src[i];
-    if (t == 0) lut->cmax = (s_misc[1] <= kLutMaxNeed && nsplit <= kLutMaxSplits) ? s_misc[1] : -1;
+    const int need = s_misc[1];
+    const int res = (need <= kLutMaxNeed && nsplit <= kLutMaxSplits) ? need : -1;
+    if constexpr (sizeof(E) == 2) {
+        if (lut) {
+            const uint4* src = reinterpret_cast<const uint4*>(lbuf);
+            uint4* dst = reinterpret_cast<uint4*>(lut->base);
+            for (int i = t; i < (int)(sizeof(lut->base) / (sizeof(uint4))); i += T) dst[i] = src[i];
+            if (t == 0) lut->cmax = res;
+        }
+    }
+    return res;
 }
 
 // Zero the payload bytes between the last written split and the codes (unused split slots after

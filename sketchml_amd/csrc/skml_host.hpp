@@ -48,6 +48,7 @@ struct skml_ctx {
     hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;  // sparse encode: its side-stream chain
     hipEvent_t after_leaf = nullptr;  // when set, recorded right after the next leaf launch
     hipEvent_t ev_switch = nullptr;   // skml_ctx_set_stream: orders the new stream after the old one
+    skml::QuantResidency qres;  // quantize pass: resident workgroups per CU, per kernel form
     skml::DevBuf sk;  // parallelQuantize: slice records + the merged sketch's export
     // FixedPointGradient: the workgroup partials of the sum of squares (kFxMaxParts, allocated once)
     skml::FxPartial* fx_part = nullptr;

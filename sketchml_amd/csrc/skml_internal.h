@@ -176,9 +176,30 @@ hipError_t launch_set_ranks(hipStream_t st, int64_t n, int bins, int64_t* ranks)
 hipError_t launch_set_splits(hipStream_t st, void* payload, int64_t n, const double* splits_dev,
                              int nsplits, double mn, double mx, int req_bins, QuantLut* lut);
 // ---- kernel launchers (skml_dense.hip) ----
-// `lut` may be null (Eytzinger / global search); req_bins sizes the kernel's LDS split table.
-hipError_t launch_quantize(hipStream_t st, const void* x, int64_t n, void* payload, const QuantLut* lut,
-                           int req_bins, int xtype = kXF32);
+// The quantize pass's resident workgroups per CU, one entry per (instantiation, dynamic LDS bytes)
+// asked of the runtime so far; lives in the context (skml_ctx::qres).
+struct QuantResidency {
+    static constexpr int kSlots = 16;
+    struct Entry {
+        int inst;
+        size_t lds;
+        int wgs;
+    } e[kSlots];
+    int used = 0, next = 0;
+    int cus = 0;  // the device's CU count
+};
+// lut == nullptr: every workgroup builds the bucket table itself from the payload's splits (the
+// quantile encodes); otherwise the caller's table (set-splits, uniform and ZipML encodes, whose
+// cmax may ask for the literal indexOf).  req_bins sizes the kernel's LDS tables.  wgs_out (debug):
+// report the resident workgroups per CU of the selected form and launch nothing.
+hipError_t launch_quantize(hipStream_t st, QuantResidency* res, const void* x, int64_t n, void* payload,
+                           const QuantLut* lut, int req_bins, int xtype = kXF32, int* wgs_out = nullptr);
+// The table the summary builds for the quantile encodes' quantize pass: none (the pass builds its
+// own).  -DSKML_Q_GLOBAL_LUT=1 (A/B builds) restores the summary-built global 16-bit table.
+#ifndef SKML_Q_GLOBAL_LUT
+#define SKML_Q_GLOBAL_LUT 0
+#endif
+inline QuantLut* summary_lut(QuantLut* lut) { return SKML_Q_GLOBAL_LUT ? lut : nullptr; }
 // out: n values of storage type otype; a 16-bit `out` needs 2-byte alignment only (16-byte stores
 // when it is 16-byte aligned, element stores otherwise), a float `out` 16-byte alignment
 hipError_t launch_decode(hipStream_t st, const void* payload, void* out, int64_t n, int otype = kXF32);

@@ -1514,8 +1514,11 @@ __device__ void summary_block(const SummaryArgs& a, SummaryShared& S, bool has_p
         hdr->reserved = 0;
     }
     // ---- quantize bucket LUT over the final split table ----
+    // (a.lut == nullptr: the quantize pass builds the table itself, per workgroup, from the splits)
     const int nsplit = bin_num - 1;
-    if (nsplit <= kMaxSamples && nsplit <= kLutMaxSplits && n > 0) {
+    if (!a.lut) {
+        // nothing to build: profiling builds stamp the end of the summary below
+    } else if (nsplit <= kMaxSamples && nsplit <= kLutMaxSplits && n > 0) {
         SKML_PROF(9);
 #ifdef SKML_PROF_SUMMARY
         if (threadIdx.x == 0) g_prof[28] = __builtin_amdgcn_s_memtime();

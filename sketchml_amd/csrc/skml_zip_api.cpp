@@ -94,7 +94,7 @@ int zip_encode_x(skml_ctx* c, const void* x, int wide, int64_t n, int32_t bins, 
     {
         KernelTimer kt(c, SKML_K_QUANTIZE);
         if (wide) HIP_TRY(launch_quantize64(c->stream, static_cast<const double*>(x), n, payload, w.lut, nullptr, bins));
-        else HIP_TRY(launch_quantize(c->stream, x, n, payload, w.lut, bins));
+        else HIP_TRY(launch_quantize(c->stream, &c->qres, x, n, payload, w.lut, bins));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SKML_OK;

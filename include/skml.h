@@ -102,7 +102,10 @@ int skml_ctx_set_stream(skml_ctx* ctx, void* hip_stream);
 #define SKML_K_DECODE 4
 #define SKML_K_DECODE_SUM 5
 #define SKML_K_SPARSE 6
-#define SKML_K_COUNT 7
+#define SKML_K_GLM_PREDICT 7 /* k_glm_predict and the reduction of loss_j */
+#define SKML_K_GLM_PLUS_BY 8
+#define SKML_K_GLM_FINISH 9
+#define SKML_K_COUNT 10
 #define SKML_TIMING_ALL (-1)
 int skml_ctx_set_timing(skml_ctx* ctx, int mask);
 /* Synchronises; total device milliseconds and launch count of kernel `kid` since the reset. */
@@ -473,6 +476,67 @@ int skml_opt_step_kv_f32(skml_ctx* ctx, const int32_t* keys_dev, const void* val
 int skml_opt_step_kv_f64(skml_ctx* ctx, const int32_t* keys_dev, const void* vals_dev, int32_t vals_fp64, int64_t nnz,
                          int64_t dim, double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
                          double* v_dev);
+
+/* ---- Mini-batch gradient: optimizer.miniBatchGradientDescent(weights, trainData, loss)
+ * (ml/objective/GradientDescent.scala:23-87, ml/objective/Loss.scala:56-137) ----
+ *
+ * The data set lives on the device, caller-owned and read-only: its CSR (row_ptr[rows + 1], col[nnz],
+ * val[nnz], label[rows]) and the same entries in (column, row) order (col_ptr[dim + 1], csc_row[nnz],
+ * csc_val[nnz]).  Every pointer is 8-byte aligned; rows and dim fit a Java int.  Preconditions, not
+ * verified (sketchml_amd/data.py verifies them): row_ptr and col_ptr ascend from 0 to nnz, the
+ * columns of a row ascend strictly inside [0, dim), csc_row ascends inside a column.  The kernels
+ * skip an entry whose column or batch position is out of range; they never read or write through it. */
+typedef struct skml_glm_data {
+    int64_t rows, dim, nnz;
+    const int64_t* row_ptr;
+    const int32_t* col;
+    const double* val;
+    const double* label;
+    const int64_t* col_ptr;
+    const int32_t* csc_row;
+    const double* csc_val;
+} skml_glm_data;
+#define SKML_LOSS_L1_LOG 0
+#define SKML_LOSS_L2_HINGE 1
+#define SKML_LOSS_L2_LOG 2
+#define SKML_LOSS_L2_SQUARE 3
+#define SKML_REG_NONE 0
+#define SKML_REG_L1 1
+#define SKML_REG_L2 2
+/* The loop of miniBatchGradientDescent over `batch` instances; instance j is row (row0 + j) mod rows
+ * (DataSet.loopingRead).  All in double, without contraction:
+ *   pre_j  = Maths.dot(w, x_j): from +0.0, w[col] * val (rounded) added in stored order
+ *   loss_j = loss.loss(pre_j, y_j),  coef_j = -1.0 * loss.grad(pre_j, y_j), branches as written
+ *            (exp and log are the device's, within 1 ulp as Java's: not bit-pinned)
+ *   grad_out[k] = from +0.0, val * coef_j (rounded) added for j = 0 .. batch - 1 in that order; +0.0
+ *            for a feature without an entry in the batch.  No atomics, no tree.  Unscaled.
+ *   *nnz_out = #{k : |grad_out[k]| > 1e-8} (toAuto's count),  *obj_loss_out = sum of loss_j by a
+ *            fixed-shape reduction (256 strided sequential sums, then a tree): deterministic, not the
+ *            reference's sequential sum; loss_out has the terms.
+ * w_dev: dim doubles (_f64) or floats (_f32, widened exactly).  pre_out, loss_out (batch doubles each)
+ * may be NULL; coef_out (batch doubles) may be NULL, a context buffer then stands in.  grad_out: dim
+ * doubles.  Synchronises once, for the two scalars, through pinned staging.  SKML_E_ARG, with nothing
+ * written: a NULL or misaligned pointer, row0 outside [0, rows), batch outside [1, rows], rows or dim
+ * outside [1, 2^31 - 1], nnz < 0, an unknown loss, grad_out overlapping an input or another output.
+ * Timed as SKML_K_GLM_PREDICT and SKML_K_GLM_PLUS_BY. */
+int skml_glm_gradient_f64(skml_ctx* ctx, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                          const double* w_dev, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                          int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_f32(skml_ctx* ctx, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                          const float* w_dev, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                          int64_t* nnz_out, double* obj_loss_out);
+/* grad.timesBy(times), then the regulariser (GradientDescent.scala:53-87), in place, on the form toAuto
+ * chose.  SKML_REG_L1 is l1Reg(grad, 0, reg_param) as written: v in [0, theta] -> Math.max(v - 0, 0),
+ * v < 0 && v >= -theta -> Math.min(v - 0, 0) (Java's max / min: -0.0 becomes +0.0).  SKML_REG_L2 is
+ * v += w[k] * reg_param (product rounded, then added); on keys and values it touches the kept keys
+ * only, as the reference does.  w_dev: dim doubles, or floats when w_fp32; may be NULL unless L2.
+ * keys_dev: strictly increasing (not verified; a key outside [0, dim) keeps timesBy and skips L2).
+ * Asynchronous.  SKML_E_ARG: NULL or misaligned pointers, dim outside [1, 2^31 - 1], nnz outside
+ * [0, dim], an unknown regulariser, values overlapping w or the keys.  Timed as SKML_K_GLM_FINISH. */
+int skml_glm_finish_dense_f64(skml_ctx* ctx, double* g_dev, int64_t dim, double times, int32_t reg_kind,
+                              double reg_param, const void* w_dev, int32_t w_fp32);
+int skml_glm_finish_kv_f64(skml_ctx* ctx, const int32_t* keys_dev, double* vals_dev, int64_t nnz, int64_t dim,
+                           double times, int32_t reg_kind, double reg_param, const void* w_dev, int32_t w_fp32);
 
 /* ---- Host memory in and out (the JNI path: a JVM float[] on its way to a socket) ---- */
 

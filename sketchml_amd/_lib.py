@@ -84,6 +84,18 @@ class OptParams(C.Structure):
                 ("beta2", C.c_double), ("beta1_t", C.c_double), ("beta2_t", C.c_double), ("eps", C.c_double)]
 
 
+SKML_LOSS_L1_LOG, SKML_LOSS_L2_HINGE, SKML_LOSS_L2_LOG, SKML_LOSS_L2_SQUARE = 0, 1, 2, 3
+SKML_REG_NONE, SKML_REG_L1, SKML_REG_L2 = 0, 1, 2
+SKML_K_GLM_PREDICT, SKML_K_GLM_PLUS_BY, SKML_K_GLM_FINISH = 7, 8, 9
+
+
+class GlmData(C.Structure):
+    """skml_glm_data (include/skml.h): a data set's CSR and its (column, row) order on the device."""
+    _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("nnz", C.c_int64), ("row_ptr", C.c_void_p),
+                ("col", C.c_void_p), ("val", C.c_void_p), ("label", C.c_void_p), ("col_ptr", C.c_void_p),
+                ("csc_row", C.c_void_p), ("csc_val", C.c_void_p)]
+
+
 class SparseGroup(C.Structure):
     _fields_ = [("size", C.c_int32), ("col_num", C.c_int32), ("hash_ids", C.c_int32 * 8),
                 ("num_intervals", C.c_int32), ("flag_kind", C.c_int32),
@@ -164,6 +176,10 @@ _SIGS = {
     "skml_opt_step_f64": (C.c_int, [vp, vp, i32, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_opt_step_kv_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_opt_step_kv_f64": (C.c_int, [vp, vp, vp, i32, i64, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_glm_gradient_f64": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_f32": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_finish_dense_f64": (C.c_int, [vp, vp, i64, C.c_double, i32, C.c_double, vp, i32]),
+    "skml_glm_finish_kv_f64": (C.c_int, [vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, vp, i32]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
     "skml_host_free": (C.c_int, [vp]),
     "skml_dense_encode_host_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), vp, C.c_size_t, szp]),

@@ -177,7 +177,7 @@ int skml_ctx_destroy(skml_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->jump_tab) (void)hipFree(c->jump_tab);
-    for (DevBuf* b : {&c->ws, &c->ws64, &c->ranks, &c->stage, &c->sk, &c->zip_ws, &c->opt_ws}) release(*b);
+    for (DevBuf* b : {&c->ws, &c->ws64, &c->ranks, &c->stage, &c->sk, &c->zip_ws, &c->opt_ws, &c->glm_ws}) release(*b);
     for (DevBuf& b : c->scratch) release(b);
     release(c->pinned, true);
     if (c->side) skml_ctx_destroy(c->side);

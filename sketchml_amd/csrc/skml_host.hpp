@@ -55,6 +55,7 @@ struct skml_ctx {
     skml::DevBuf zip_ws;  // ZipMLQuantizer: keys, sorted copy, prefix sums, errors, splitIndex
     int zip_rounds = 0;   // halving rounds of the last successful ZipML encode (skml_debug_zip_rounds)
     skml::DevBuf opt_ws;  // optimiser step: the live counter of SKML_OPT_AUTO
+    skml::DevBuf glm_ws;  // mini-batch gradient: live counter, objLoss, and coef / loss_j when the caller keeps none
     skml::DevBuf stage;   // staging
     // sparse path: device scratch slots and pinned host staging
     skml::DevBuf scratch[skml::kScratchSlots];

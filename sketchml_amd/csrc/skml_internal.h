@@ -269,8 +269,22 @@ hipError_t launch_fixed_decode_sum_step(hipStream_t st, const void* payloads, in
                                         double scale, int bits, const OptConsts& k, int wide, void* w, void* m, void* v);
 hipError_t launch_fixed_decode_sum_live(hipStream_t st, const void* payloads, int P, size_t stride, int64_t n,
                                         double scale, int bits, unsigned long long* count);
+// ---- mini-batch gradient (skml_glm.hip; ml/objective/GradientDescent.scala:23-87, Loss.scala:56-137) ----
+// `wide`: w holds doubles (else floats, widened exactly).  lanes: 1, 8 or 64 lanes per row
+// (glm_lanes_per_row picks from the data set's mean row length).  pre / loss may be null.
+int glm_lanes_per_row(int64_t nnz, int64_t rows);
+hipError_t launch_glm_predict(hipStream_t st, const skml_glm_data& d, int64_t row0, int64_t batch, int loss_kind,
+                              const void* w, int wide, int lanes, double* pre, double* coef, double* loss);
+// *obj = the sum of loss[0 .. batch) by one workgroup: 256 strided sequential sums, then a fixed tree
+hipError_t launch_glm_loss_sum(hipStream_t st, const double* loss, int64_t batch, double* obj);
+// g[k] for every k in [0, dim) in plusBy's order; *count (zeroed by the caller) += #{|g[k]| > 1e-8}
+hipError_t launch_glm_plus_by(hipStream_t st, const skml_glm_data& d, int64_t row0, int64_t batch, const double* coef,
+                              double* g, unsigned long long* count);
+// timesBy(times), then the regulariser, in place; keys null: the dense form over dim values
+hipError_t launch_glm_finish(hipStream_t st, const int32_t* keys, double* vals, int64_t n, int64_t dim, double times,
+                             int reg_kind, double reg_param, const void* w, int wide);
 // ---- ZipMLQuantizer (skml_zip.hip) ----
-constexpr int kZipMinBins = 4;   // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
+constexpr int kZipMinBins = 4;  // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
 constexpr int kZipTail = 4096;   // splitNum at which the rounds move into one workgroup's LDS
 enum : int { kZipOk = 0, kZipThrZero = 1, kZipNoProgress = 2 };
 // Device state of one call: the select's walk, the round's result, the search's outcome.

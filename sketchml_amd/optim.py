@@ -6,7 +6,12 @@ The weight is a device tensor (float64 as the reference's DenseVector, or float3
 v are tensors of the weight's dtype that the optimiser owns.  All arithmetic runs in double in the
 reference's operation order inside libskml's kernels; this module keeps what the reference keeps
 on the host: the epoch / batch counters, the learning-rate decay, the beta_t products and the
-dispatch on the gradient's kind.  miniBatchGradientDescent and the regularisers are not here.
+dispatch on the gradient's kind.
+
+miniBatchGradientDescent (GradientDescent.scala:23-87) is here too, over skml_glm_gradient_* and
+skml_glm_finish_*: the predictions, losses and plusBy of a batch of a data.DataSet, toAuto, timesBy
+and the regularisers run on the device; objLoss and regLoss, which the reference only logs, are
+the two scalars that come back.
 """
 from __future__ import annotations
 
@@ -18,7 +23,8 @@ import torch
 from . import _lib
 from .context import LOWP_DTYPES, as_device_f32, as_device_values, get_context
 from .exceptions import SketchMLException, check
-from .gradient import EPS, Kind
+from .gradient import EPS, DenseDoubleGradient, Kind, SparseDoubleGradient, auto_dense
+from .sparse import to_sparse
 
 ALL, LIVE, AUTO = _lib.SKML_OPT_ALL, _lib.SKML_OPT_LIVE, _lib.SKML_OPT_AUTO
 
@@ -32,6 +38,42 @@ def _gradient_values(values) -> torch.Tensor:
     return as_device_f32(x) if x.dtype in LOWP_DTYPES else x
 
 
+def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, want_pre: bool = False):
+    """skml_glm_gradient_*: the loop of miniBatchGradientDescent over the rows (row0 + j) mod size,
+    j < batch, of a data.DataSet.  Returns a dict of float64 device tensors and two host scalars:
+    grad (dim values, unscaled), coef (-1.0 * loss.grad per instance), loss (per instance), pre (when
+    asked for), nnz (toAuto's count of |grad| > 1e-8) and objLoss."""
+    dev = weight.device
+    if dataSet.device != dev:
+        raise SketchMLException(f"the data set lives on {dataSet.device}, the weight on {dev}")
+    data = dataSet.glm_data()
+    out = {"grad": torch.empty(dataSet.dim, dtype=torch.float64, device=dev),
+           "coef": torch.empty(batch, dtype=torch.float64, device=dev),
+           "loss": torch.empty(batch, dtype=torch.float64, device=dev),
+           "pre": torch.empty(batch, dtype=torch.float64, device=dev) if want_pre else None}
+    nnz, obj = C.c_int64(), C.c_double()
+    fn = _lib.lib.skml_glm_gradient_f64 if weight.dtype == torch.float64 else _lib.lib.skml_glm_gradient_f32
+    check(fn(get_context(dev).handle, C.byref(data), int(row0), int(batch), int(loss.kind), _ptr(weight), _ptr(out["pre"]),
+             _ptr(out["coef"]), _ptr(out["loss"]), _ptr(out["grad"]), C.byref(nnz), C.byref(obj)), "glm_gradient")
+    out["nnz"], out["objLoss"] = int(nnz.value), float(obj.value)
+    return out
+
+
+def finish_gradient(grad, times: float, loss, weight: torch.Tensor) -> None:
+    """skml_glm_finish_*: grad.timesBy(times), then l1Reg / l2Reg when the loss has one on, in place on
+    a DenseDoubleGradient or a SparseDoubleGradient of float64 values."""
+    h = get_context(weight.device).handle
+    reg, lam, w32 = loss.reg_kind(), float(loss.getRegParam), int(weight.dtype == torch.float32)
+    if grad.kind() == Kind.DenseDouble:
+        check(_lib.lib.skml_glm_finish_dense_f64(h, _ptr(grad.values), grad.dim, float(times), reg, lam, _ptr(weight), w32),
+              "glm_finish_dense")
+    elif grad.kind() == Kind.SparseDouble:
+        check(_lib.lib.skml_glm_finish_kv_f64(h, _ptr(grad.indices), _ptr(grad.values), grad.indices.numel(), grad.dim,
+                                              float(times), reg, lam, _ptr(weight), w32), "glm_finish_kv")
+    else:
+        raise SketchMLException(f"Cannot regularize {grad.kind().value} kind of gradients")
+
+
 class GradientDescent:
     """ml/objective/GradientDescent.scala: w -= g * lr with lr = lr_0 / sqrt(1 + decay * epoch)."""
 
@@ -42,6 +84,31 @@ class GradientDescent:
         self.epoch = 0
         self.batch = 0
         self.batchNum = float(int(math.ceil(1.0 / batchSpRatio)))  # GradientDescent.scala:21
+
+    def miniBatchGradientDescent(self, weight: torch.Tensor, dataSet, loss):
+        """GradientDescent.scala:23-51: (grad, batchSize, objLoss, regLoss) of the next
+        (size * batchSpRatio).toInt instances of dataSet.loopingRead.  grad is toAuto's choice, a
+        DenseDoubleGradient or a SparseDoubleGradient of float64 device tensors, scaled by
+        1.0 / batchSize and regularised.  objLoss is a fixed-shape device sum of the per-instance
+        losses, which stay in self.lastLoss for a caller who wants the sequential sum."""
+        batchSize = int(dataSet.size * self.batchSpRatio)
+        if batchSize == 0 or self.batchSpRatio > 1:
+            raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
+                                    f"{batchSize}: the reference divides by zero, or reads an instance twice")
+        self._check_weight(weight)
+        if dataSet.dim != self.dim:
+            raise SketchMLException(f"the data set has {dataSet.dim} features, the optimiser {self.dim}")
+        out = batch_gradient(weight, dataSet, dataSet.take(batchSize), batchSize, loss)
+        self.lastLoss = out["loss"]
+        if auto_dense(out["nnz"], self.dim):
+            grad = DenseDoubleGradient(self.dim, out["grad"])
+        else:
+            keys, vals = to_sparse(out["grad"])  # toSparse of the unscaled values
+            grad = SparseDoubleGradient(self.dim, keys, vals)
+        finish_gradient(grad, 1.0 / batchSize, loss, weight)
+        regLoss = float(loss.getReg(weight))
+        self.nextBatch()
+        return grad, batchSize, out["objLoss"], regLoss
 
     def nextBatch(self) -> None:
         """The counters' step at the end of miniBatchGradientDescent (GradientDescent.scala:48-49)."""

@@ -105,7 +105,11 @@ int skml_ctx_set_stream(skml_ctx* ctx, void* hip_stream);
 #define SKML_K_GLM_PREDICT 7 /* k_glm_predict and the reduction of loss_j */
 #define SKML_K_GLM_PLUS_BY 8
 #define SKML_K_GLM_FINISH 9
-#define SKML_K_COUNT 10
+#define SKML_K_GLM_VALID 10  /* k_glm_valid */
+#define SKML_K_SEQ_SUM 11    /* the ordered sum (or, with SKML_VALID_TREE_SUM, the tree sum) */
+#define SKML_K_VALID_SORT 12 /* the keys and one launch per pass of the key-and-payload sort */
+#define SKML_K_VALID_RANK 13 /* the rank sum */
+#define SKML_K_COUNT 14
 #define SKML_TIMING_ALL (-1)
 int skml_ctx_set_timing(skml_ctx* ctx, int mask);
 /* Synchronises; total device milliseconds and launch count of kernel `kid` since the reset. */
@@ -537,6 +541,63 @@ int skml_glm_finish_dense_f64(skml_ctx* ctx, double* g_dev, int64_t dim, double 
                               double reg_param, const void* w_dev, int32_t w_fp32);
 int skml_glm_finish_kv_f64(skml_ctx* ctx, const int32_t* keys_dev, double* vals_dev, int64_t nnz, int64_t dim,
                            double times, int32_t reg_kind, double reg_param, const void* w_dev, int32_t w_fp32);
+
+/* ---- Validation pass: ValidationUtil.calLossPrecision / calLossAucPrecision
+ * (ml/util/ValidationUtil.scala:12-93, sketch/util/Sort.java:168-259) ----
+ *
+ * For every instance i of the data set, in order, all in double without contraction:
+ *   pre_i  = Maths.dot(w, x_i), the bits of skml_glm_gradient_*'s pre
+ *   z      = pre_i * label_i (one rounded product): z > 0 -> truePos if pre_i > 0 else trueNeg;
+ *            z < 0 -> falsePos if pre_i > 0 else falseNeg; z == 0 (an underflow, a zero label, an
+ *            empty row) or NaN -> no counter moves
+ *   loss_i = loss.loss(pre_i, label_i)
+ *   loss   = ((0.0 + loss_0) + loss_1) + ..., one rounded add after the other: the reference's bits
+ *            given the loss_i.  With SKML_VALID_TREE_SUM the fixed-shape sum of skml_glm_gradient_*'s
+ *            objLoss instead (deterministic and faster, not the reference's order).
+ * With SKML_VALID_AUC also the sort of (score, label) ascending by score and
+ *   pos = #{label == 1.0} (M),  neg = num - pos (N),
+ *   rank_sum = the sum of the 0-based sorted positions that hold a label == 1.0 (sigma), an exact integer;
+ * the caller forms auc = (sigma - (M + 1) * M / 2) / M / N as the reference writes it.
+ *
+ * The order of the sort -- the tie rule.  The reference sorts with a quicksort whose comparator calls two
+ * scores equal when they differ by less than 1e-11; that relation is not transitive and the order
+ * inside a group of near-equal scores depends on the pivots (its output need not even ascend).  Here
+ * scores are ordered by their IEEE total-order key: -0.0 before +0.0, infinities are ordinary values,
+ * and equal scores keep instance order (a stable sort).  rank_sum equals the reference's whenever all
+ * gaps between distinct sorted scores exceed 1e-11 and no score repeats; otherwise it is this rule's.
+ * A NaN score is counted in nan_scores and makes the AUC undefined (the caller reports NaN).
+ * The reference accumulates sigma in double, exact while n (n - 1) / 2 < 2^53 (n <= 2^27); above that
+ * the integer rank_sum converted once is the documented deviation. */
+#define SKML_VALID_AUC 1
+#define SKML_VALID_TREE_SUM 2
+typedef struct skml_valid_result {
+    double loss;        /* validLoss: the sum, not the mean */
+    int64_t true_pos, true_neg, false_pos, false_neg;
+    int64_t num;        /* validNum = rows */
+    int64_t pos, neg;   /* M, N; 0 without SKML_VALID_AUC */
+    uint64_t rank_sum;  /* sigma; 0 without SKML_VALID_AUC */
+    int64_t nan_scores; /* the NaN predictions */
+} skml_valid_result;
+/* data: as skml_glm_gradient_*, except that col_ptr, csc_row and csc_val are not read and may be NULL.
+ * w_dev: dim doubles (_f64) or floats (_f32, widened exactly).  pre_out, loss_out (rows doubles each)
+ * may be NULL; the context's buffer then stands in.  One read-back through pinned staging after one
+ * synchronisation.  SKML_E_ARG, with nothing written: a NULL or misaligned pointer, rows or dim
+ * outside [1, 2^31 - 1], nnz < 0, an unknown loss or flag bit, an output overlapping an input or the
+ * other output.  Timed as SKML_K_GLM_VALID, SKML_K_SEQ_SUM, SKML_K_VALID_SORT, SKML_K_VALID_RANK. */
+int skml_glm_validate_f64(skml_ctx* ctx, const skml_glm_data* data, int32_t loss_kind, const double* w_dev, int32_t flags,
+                          double* pre_out, double* loss_out, skml_valid_result* out);
+int skml_glm_validate_f32(skml_ctx* ctx, const skml_glm_data* data, int32_t loss_kind, const float* w_dev, int32_t flags,
+                          double* pre_out, double* loss_out, skml_valid_result* out);
+/* The AUC stage alone over n scores and labels on the device (n in [1, 2^31 - 1], 8-byte aligned):
+ * *pos, *neg, *rank_sum and *nan_scores as above; order_out (optional, n int32 on the device, 4-byte
+ * aligned, not overlapping the inputs) receives the sorted permutation: order_out[p] = the instance at
+ * sorted position p.  Synchronises once.  skml_glm_validate_* runs the same code. */
+int skml_auc_rank_sum(skml_ctx* ctx, const double* scores_dev, const double* labels_dev, int64_t n, int32_t* order_out,
+                      int64_t* pos, int64_t* neg, uint64_t* rank_sum, int64_t* nan_scores);
+/* *sum = ((0.0 + x[0]) + x[1]) + ... + x[n - 1], one rounded add after the other (the reference's
+ * `objLoss += ...` and `validLoss += ...`): n in [1, 2^31 - 1] doubles on the device, 8-byte aligned.
+ * A chain of n dependent additions run by one wave.  Synchronises once. */
+int skml_glm_seq_sum(skml_ctx* ctx, const double* x_dev, int64_t n, double* sum);
 
 /* ---- Host memory in and out (the JNI path: a JVM float[] on its way to a socket) ---- */
 

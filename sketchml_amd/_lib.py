@@ -87,6 +87,8 @@ class OptParams(C.Structure):
 SKML_LOSS_L1_LOG, SKML_LOSS_L2_HINGE, SKML_LOSS_L2_LOG, SKML_LOSS_L2_SQUARE = 0, 1, 2, 3
 SKML_REG_NONE, SKML_REG_L1, SKML_REG_L2 = 0, 1, 2
 SKML_K_GLM_PREDICT, SKML_K_GLM_PLUS_BY, SKML_K_GLM_FINISH = 7, 8, 9
+SKML_K_GLM_VALID, SKML_K_SEQ_SUM, SKML_K_VALID_SORT, SKML_K_VALID_RANK = 10, 11, 12, 13
+SKML_VALID_AUC, SKML_VALID_TREE_SUM = 1, 2
 
 
 class GlmData(C.Structure):
@@ -94,6 +96,13 @@ class GlmData(C.Structure):
     _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("nnz", C.c_int64), ("row_ptr", C.c_void_p),
                 ("col", C.c_void_p), ("val", C.c_void_p), ("label", C.c_void_p), ("col_ptr", C.c_void_p),
                 ("csc_row", C.c_void_p), ("csc_val", C.c_void_p)]
+
+
+class ValidResult(C.Structure):
+    """skml_valid_result (include/skml.h): what one validation pass reads back."""
+    _fields_ = [("loss", C.c_double), ("true_pos", C.c_int64), ("true_neg", C.c_int64), ("false_pos", C.c_int64),
+                ("false_neg", C.c_int64), ("num", C.c_int64), ("pos", C.c_int64), ("neg", C.c_int64),
+                ("rank_sum", C.c_uint64), ("nan_scores", C.c_int64)]
 
 
 class SparseGroup(C.Structure):
@@ -180,6 +189,10 @@ _SIGS = {
     "skml_glm_gradient_f32": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_glm_finish_dense_f64": (C.c_int, [vp, vp, i64, C.c_double, i32, C.c_double, vp, i32]),
     "skml_glm_finish_kv_f64": (C.c_int, [vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, vp, i32]),
+    "skml_glm_validate_f64": (C.c_int, [vp, C.POINTER(GlmData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_glm_validate_f32": (C.c_int, [vp, C.POINTER(GlmData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_auc_rank_sum": (C.c_int, [vp, vp, vp, i64, vp, i64p, i64p, C.POINTER(C.c_uint64), i64p]),
+    "skml_glm_seq_sum": (C.c_int, [vp, vp, i64, dblp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
     "skml_host_free": (C.c_int, [vp]),
     "skml_dense_encode_host_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), vp, C.c_size_t, szp]),

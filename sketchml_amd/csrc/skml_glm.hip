@@ -4,6 +4,9 @@
 //                                (gathers and products across lanes, the add chain in entry order),
 //                                then loss.loss / -1.0 * loss.grad
 //   k_glm_loss_sum               sum of loss_j: one workgroup, strided sequential sums, a fixed tree
+//   k_glm_valid<W, LOSS, LPR>    the validation pass (ml/util/ValidationUtil.scala:12-41): the same row dot
+//                                over every row, loss.loss, the four confusion counts
+//   k_glm_seq_sum                sum of n doubles in index order, the reference's bits: one wave
 //   k_glm_plus_by                g[k] per column in batch order: a lane for a column with a short
 //                                window, the wave for a long one; +0.0 where the window is empty;
 //                                toAuto's live count on the way
@@ -16,6 +19,7 @@
 #include "skml_device.hpp"
 #include "skml_glm.hpp"
 #include "skml_opt.hpp"
+#include "skml_valid.hpp"
 
 namespace skml {
 
@@ -88,6 +92,51 @@ __device__ __forceinline__ void glm_loss(double pre, double y, double& loss, dou
     }
 }
 
+// Maths.dot(w, x_row) over the row's entries [s, e) by the row's LPR lanes (sub = the lane's place among
+// them): the gathers and products across lanes, the adds one after the other in stored order from
+// +0.0.  Every lane of a wave reaches the call (the cross-lane reads need them all); with LPR == 64
+// s and e are taken from lane 0.  Every lane of the row returns the sum.
+template <typename W, int LPR>
+__device__ __forceinline__ double glm_row_dot(const skml_glm_data& d, const W* __restrict__ w, int64_t s, int64_t e,
+                                              int sub) {
+    double acc = 0.0;
+    if constexpr (LPR == 1) {
+        for (int64_t i = s; i < e; i++) {
+            const int32_t c = d.col[i];
+            if ((uint32_t)c >= (uint64_t)d.dim) continue;
+            const double p = (double)w[c] * d.val[i];
+            acc += p;
+        }
+    } else if constexpr (LPR == 64) {
+        const int64_t us = uniform_i64(s, 0), ue = uniform_i64(e, 0);  // one row per wave
+        for (int64_t b = us; b < ue; b += 64) {
+            const int64_t i = b + sub;
+            double p = 0.0;
+            if (i < ue) {
+                const int32_t c = d.col[i];
+                if ((uint32_t)c < (uint64_t)d.dim) p = (double)w[c] * d.val[i];
+            }
+            acc = ordered_add64(acc, p, (int)std::min<int64_t>(64, ue - b));
+        }
+    } else {
+        const int64_t len = e - s;
+        for (int64_t b = 0; __any(b < len); b += LPR) {
+            const int64_t i = s + b + sub;
+            double p = 0.0;
+            if (i < e) {
+                const int32_t c = d.col[i];
+                if ((uint32_t)c < (uint64_t)d.dim) p = (double)w[c] * d.val[i];
+            }
+#pragma unroll
+            for (int t = 0; t < LPR; t++) {
+                const double q = __shfl(p, t, LPR);
+                if (b + t < len) acc += q;
+            }
+        }
+    }
+    return acc;
+}
+
 template <typename W, int LOSS, int LPR>
 __global__ __launch_bounds__(256) void k_glm_predict(skml_glm_data d, GlmWindow win, int64_t batch,
                                                      const W* __restrict__ w, double* __restrict__ pre,
@@ -105,41 +154,7 @@ __global__ __launch_bounds__(256) void k_glm_predict(skml_glm_data d, GlmWindow 
             e = clamp_ptr(d.row_ptr[row + 1], d.nnz);
             if (e < s) e = s;
         }
-        double acc = 0.0;
-        if constexpr (LPR == 1) {
-            for (int64_t i = s; i < e; i++) {
-                const int32_t c = d.col[i];
-                if ((uint32_t)c >= (uint64_t)d.dim) continue;
-                const double p = (double)w[c] * d.val[i];
-                acc += p;
-            }
-        } else if constexpr (LPR == 64) {
-            const int64_t us = uniform_i64(s, 0), ue = uniform_i64(e, 0);  // one row per wave
-            for (int64_t b = us; b < ue; b += 64) {
-                const int64_t i = b + sub;
-                double p = 0.0;
-                if (i < ue) {
-                    const int32_t c = d.col[i];
-                    if ((uint32_t)c < (uint64_t)d.dim) p = (double)w[c] * d.val[i];
-                }
-                acc = ordered_add64(acc, p, (int)std::min<int64_t>(64, ue - b));
-            }
-        } else {
-            const int64_t len = e - s;
-            for (int64_t b = 0; __any(b < len); b += LPR) {
-                const int64_t i = s + b + sub;
-                double p = 0.0;
-                if (i < e) {
-                    const int32_t c = d.col[i];
-                    if ((uint32_t)c < (uint64_t)d.dim) p = (double)w[c] * d.val[i];
-                }
-#pragma unroll
-                for (int t = 0; t < LPR; t++) {
-                    const double q = __shfl(p, t, LPR);
-                    if (b + t < len) acc += q;
-                }
-            }
-        }
+        const double acc = glm_row_dot<W, LPR>(d, w, s, e, sub);
         if (on && sub == 0) {
             double l, g;
             glm_loss<LOSS>(acc, d.label[row], l, g);
@@ -148,6 +163,92 @@ __global__ __launch_bounds__(256) void k_glm_predict(skml_glm_data d, GlmWindow 
             if (loss) loss[j] = l;
         }
     }
+}
+
+// The validation pass (ml/util/ValidationUtil.scala:21-31) over every row of the data set: the row dot
+// of k_glm_predict, loss.loss, and the instance's class.  cnt[0 .. 4) += truePos, trueNeg, falsePos,
+// falseNeg and cnt[4] += the NaN scores, as LiveCount counts: a ballot and a popcount per wave, one LDS
+// add per wave, one global atomic per workgroup and counter (integer sums: no order to depend on).
+// The column-order arrays of d are not read.
+constexpr int kValidCounters = 5;
+template <typename W, int LOSS, int LPR>
+__global__ __launch_bounds__(256) void k_glm_valid(skml_glm_data d, const W* __restrict__ w, double* __restrict__ pre,
+                                                   double* __restrict__ loss, unsigned long long* __restrict__ cnt) {
+    __shared__ unsigned long long s_cnt[kValidCounters];
+    constexpr int kRows = 256 / LPR;
+    const int sub = threadIdx.x % LPR;
+    unsigned long long wave[kValidCounters] = {0, 0, 0, 0, 0};  // wave-uniform
+    // the trip count is the workgroup's: the cross-lane reads and the ballots need every lane of a wave
+    for (int64_t jb = (int64_t)blockIdx.x * kRows; jb < d.rows; jb += (int64_t)gridDim.x * kRows) {
+        const int64_t row = jb + threadIdx.x / LPR;
+        const bool on = row < d.rows;
+        int64_t s = 0, e = 0;
+        if (on) {
+            s = clamp_ptr(d.row_ptr[row], d.nnz);
+            e = clamp_ptr(d.row_ptr[row + 1], d.nnz);
+            if (e < s) e = s;
+        }
+        const double acc = glm_row_dot<W, LPR>(d, w, s, e, sub);
+        int cls = kValidNone;
+        bool nan = false;
+        if (on && sub == 0) {
+            const double y = d.label[row];
+            double l, g;
+            glm_loss<LOSS>(acc, y, l, g);
+            if (pre) pre[row] = acc;
+            loss[row] = l;
+            cls = valid_class(acc, y);
+            nan = acc != acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) wave[k] += (unsigned long long)__popcll(__ballot(cls == k + 1));
+        wave[4] += (unsigned long long)__popcll(__ballot(nan));
+    }
+    if (threadIdx.x < kValidCounters) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kValidCounters; k++)
+            if (wave[k]) atomicAdd(&s_cnt[k], wave[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < kValidCounters && s_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+// acc = 0.0; for i: acc += x[i], the reference's `validLoss += ...` / `objLoss += ...` bit for bit: a
+// chain of n dependent adds, so one wave of one workgroup.  The wave stages kSeqStep values through its
+// LDS slots and adds them from broadcast reads while the next kSeqStep are in flight
+// (glm_wave_range_sum's pattern; the chunk walk is skml_valid.hpp's).
+__device__ __forceinline__ void seq_load(double (&p)[kSeqU], const double* __restrict__ x, int64_t b, int64_t n, int lane) {
+#pragma unroll
+    for (int u = 0; u < kSeqU; u++) {
+        const int64_t i = seq_index(b, u, lane);
+        p[u] = i < n ? x[i] : 0.0;
+    }
+}
+__global__ __launch_bounds__(64) void k_glm_seq_sum(const double* __restrict__ x, int64_t n, double* __restrict__ out) {
+    __shared__ double slots[kSeqStep];
+    const int lane = threadIdx.x;
+    double acc = 0.0;
+    double nxt[kSeqU];
+    seq_load(nxt, x, 0, n, lane);
+    for (int64_t b = 0; b < n; b += kSeqStep) {
+#pragma unroll
+        for (int u = 0; u < kSeqU; u++) slots[u * 64 + lane] = nxt[u];
+        if (b + kSeqStep < n) seq_load(nxt, x, b + kSeqStep, n, lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int u = 0; u < kSeqU; u++) {
+            const int cnt = seq_chunk_count(n, b, u);
+            if (cnt > 0) acc = ordered_add_lds(acc, slots + u * 64, cnt);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (lane == 0) *out = acc;
 }
 
 // Fixed shape, so the same bits on every run: thread t adds loss[t], loss[t + 1024], ... from +0.0,
@@ -328,6 +429,42 @@ hipError_t launch_glm_predict(hipStream_t st, const skml_glm_data& d, int64_t ro
     const GlmWindow win = glm_window(d.rows, row0, batch);
     return wide ? launch_predict<double>(st, d, win, batch, loss_kind, w, lanes, pre, coef, loss)
                 : launch_predict<float>(st, d, win, batch, loss_kind, w, lanes, pre, coef, loss);
+}
+
+template <typename W, int LOSS>
+static void launch_valid_w(hipStream_t st, const skml_glm_data& d, const void* w, int lanes, double* pre, double* loss,
+                           unsigned long long* cnt) {
+    const W* wp = static_cast<const W*>(w);
+    if (lanes == 1)
+        hipLaunchKernelGGL((k_glm_valid<W, LOSS, 1>), dim3(glm_grid(d.rows, 256, 65536)), dim3(256), 0, st, d, wp, pre, loss, cnt);
+    else if (lanes == 8)
+        hipLaunchKernelGGL((k_glm_valid<W, LOSS, 8>), dim3(glm_grid(d.rows, 32, 65536)), dim3(256), 0, st, d, wp, pre, loss, cnt);
+    else
+        hipLaunchKernelGGL((k_glm_valid<W, LOSS, 64>), dim3(glm_grid(d.rows, 4, 65536)), dim3(256), 0, st, d, wp, pre, loss, cnt);
+}
+template <typename W>
+static hipError_t launch_valid(hipStream_t st, const skml_glm_data& d, int loss_kind, const void* w, int lanes, double* pre,
+                               double* loss, unsigned long long* cnt) {
+    switch (loss_kind) {
+        case SKML_LOSS_L1_LOG:
+        case SKML_LOSS_L2_LOG: launch_valid_w<W, kGlmLog>(st, d, w, lanes, pre, loss, cnt); break;
+        case SKML_LOSS_L2_HINGE: launch_valid_w<W, kGlmHinge>(st, d, w, lanes, pre, loss, cnt); break;
+        case SKML_LOSS_L2_SQUARE: launch_valid_w<W, kGlmSquare>(st, d, w, lanes, pre, loss, cnt); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_glm_valid(hipStream_t st, const skml_glm_data& d, int loss_kind, const void* w, int wide, int lanes,
+                            double* pre, double* loss, unsigned long long* cnt) {
+    if (d.rows < 1 || !loss || !cnt || (lanes != 1 && lanes != 8 && lanes != 64)) return hipErrorInvalidValue;
+    return wide ? launch_valid<double>(st, d, loss_kind, w, lanes, pre, loss, cnt)
+                : launch_valid<float>(st, d, loss_kind, w, lanes, pre, loss, cnt);
+}
+
+hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out) {
+    hipLaunchKernelGGL(k_glm_seq_sum, dim3(1), dim3(64), 0, st, x, n, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_glm_loss_sum(hipStream_t st, const double* loss, int64_t batch, double* obj) {

@@ -8,21 +8,6 @@ using namespace skml;
 
 namespace {
 
-struct Range {
-    const void* p;
-    size_t bytes;
-    const char* name;
-};
-
-bool overlap(const Range& a, const Range& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
-bool aligned8(const void* p) { return ((uintptr_t)p) % 8 == 0; }
-
-constexpr int64_t kJavaIntMax = 0x7FFFFFFFLL;
 constexpr size_t kGlmHead = 256;  // the live counter and objLoss, ahead of the stand-in arrays
 
 int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w, int wide,

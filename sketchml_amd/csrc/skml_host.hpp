@@ -135,6 +135,21 @@ inline const skml_params* params_or_default(const skml_params* p, skml_params* d
     return def;
 }
 
+// What the argument checks of the entries share: a named byte range of a caller's array (a NULL or empty
+// range overlaps nothing), 8-byte alignment, and the largest length a Java int holds.
+struct Range {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+inline bool overlap(const Range& a, const Range& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+inline bool aligned8(const void* p) { return ((uintptr_t)p) % 8 == 0; }
+constexpr int64_t kJavaIntMax = 0x7FFFFFFFLL;
+
 inline bool valid_payload_ptr(const void* p) { return p && (((uintptr_t)p) % 256 == 0); }
 
 // ---- the dense workspace (skml_dense_api.cpp), also the home of the quantize LUT that the

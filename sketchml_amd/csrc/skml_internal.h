@@ -283,6 +283,28 @@ hipError_t launch_glm_plus_by(hipStream_t st, const skml_glm_data& d, int64_t ro
 // timesBy(times), then the regulariser, in place; keys null: the dense form over dim values
 hipError_t launch_glm_finish(hipStream_t st, const int32_t* keys, double* vals, int64_t n, int64_t dim, double times,
                              int reg_kind, double reg_param, const void* w, int wide);
+// ---- validation pass (skml_glm.hip, skml_valid.hip; ml/util/ValidationUtil.scala:12-93) ----
+// Every row of d: pre (may be null), loss, and cnt[0 .. 5) += truePos, trueNeg, falsePos, falseNeg, NaN
+// scores (zeroed by the caller on the same stream).  d's column-order arrays are not read.
+hipError_t launch_glm_valid(hipStream_t st, const skml_glm_data& d, int loss_kind, const void* w, int wide, int lanes,
+                            double* pre, double* loss, unsigned long long* cnt);
+// *out = ((0.0 + x[0]) + x[1]) + ... + x[n - 1] by one wave
+hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out);
+// Scratch of the key-and-payload sort over n scores; the sorted permutation ends in idx_a.
+struct ValidAucScratch {
+    uint64_t *keys_a, *keys_b;
+    uint32_t *idx_a, *idx_b;
+    uint32_t *hist, *hist_tmp;
+};
+size_t valid_auc_layout(int64_t n, ValidAucScratch* out, char* base);
+// *nan_count (zeroed by the caller) += the NaN scores
+hipError_t launch_valid_keys(hipStream_t st, const double* score, int64_t n, const ValidAucScratch& s,
+                             unsigned long long* nan_count);
+// pass 0 .. 7 in order
+hipError_t launch_valid_sort_pass(hipStream_t st, int64_t n, int pass, const ValidAucScratch& s);
+// res[0] += sigma, res[1] += M (zeroed by the caller); order (may be null): the permutation as int32
+hipError_t launch_valid_rank_sum(hipStream_t st, const ValidAucScratch& s, const double* label, int64_t n, int32_t* order,
+                                 unsigned long long* res);
 // ---- ZipMLQuantizer (skml_zip.hip) ----
 constexpr int kZipMinBins = 4;  // bin_num 2 and 3 reach thrNum = 0 (selectKthLargest of nothing)
 constexpr int kZipTail = 4096;   // splitNum at which the rounds move into one workgroup's LDS
@@ -328,6 +350,12 @@ hipError_t launch_zip_round(hipStream_t st, const int32_t* idx, int32_t* idx_out
 // the rounds from split_num <= kZipTail on (or none), then s.splits and s.state's outcome
 hipError_t launch_zip_finish(hipStream_t st, const int32_t* idx, int64_t split_num, int64_t n, int bins,
                              const double* r, const double* t, const double* sorted, const ZipScratch& s);
+// The sort's pieces that the validation pass's key-and-payload sort (skml_valid.hip) runs as they are:
+// the digit counts of the kZsTile-key tiles of uint64 keys, digit-major (hist[d * nblocks + b]), and the
+// exclusive scan of uint32 in place (tmp: zip_scan_u32_tmp(n) entries).
+hipError_t launch_zip_hist64(hipStream_t st, const uint64_t* keys, int64_t n, int pass, uint32_t* hist, int nblocks);
+hipError_t zip_scan_u32(hipStream_t st, uint32_t* data, int64_t n, uint32_t* tmp);
+size_t zip_scan_u32_tmp(int64_t n);
 // ---- kernel launchers (skml_f64.hip) ----
 hipError_t launch_summary64(hipStream_t st, const double* x, int64_t n, const LeafPartial64* part, int64_t nparts,
                             const double* roots, const int64_t* ranks, int req_bins, int dedup, void* payload,

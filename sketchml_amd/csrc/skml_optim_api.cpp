@@ -10,18 +10,6 @@ using namespace skml;
 
 namespace {
 
-struct Range {
-    const void* p;
-    size_t bytes;
-    const char* name;
-};
-
-bool overlap(const Range& a, const Range& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 // The checks every entry shares, none of which needs a device: the context, the parameters, the
 // state pointers (16-byte aligned, m and v exactly when Adam), and no two of `r` overlapping.
 // r[0..3) are w, m, v; the entry appends its inputs.

@@ -20,9 +20,6 @@
 
 namespace skml {
 
-constexpr int kZsThreads = 256;
-constexpr int kZsWaves = kZsThreads / 64;
-constexpr int kZsTile = kZsThreads * 32;  // keys per workgroup of a sort pass
 constexpr int kZuItems = 8;
 constexpr int kZuBlock = kZsThreads * kZuItems;  // 2,048 entries per workgroup of the integer scan and of a round
 constexpr int kZfThreads = 1024;                 // k_zip_finish
@@ -86,7 +83,6 @@ __global__ __launch_bounds__(kZsThreads) void k_zip_hist(const K* __restrict__ k
 // digit are turned into offsets by that digit's thread, which also moves the digit's base on.  Two
 // workgroup barriers per 1,024 keys.  Every position is below n because the offsets are the
 // exclusive scan of the counts of these same tiles.
-constexpr int kZsRows = 4;
 static_assert(kZsTile % (kZsRows * kZsThreads) == 0, "a tile is whole steps");
 template <typename K>
 __global__ __launch_bounds__(kZsThreads) void k_zip_scatter(const K* __restrict__ in, K* __restrict__ out, int64_t n,
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(kZsThreads) void k_zip_add_u32(uint32_t* __restrict
 static int64_t zu_blocks(int64_t n) { return (n + kZuBlock - 1) / kZuBlock; }
 
 // tmp: zip_scan_u32_tmp(n) entries
-static hipError_t zip_scan_u32(hipStream_t st, uint32_t* data, int64_t n, uint32_t* tmp) {
+hipError_t zip_scan_u32(hipStream_t st, uint32_t* data, int64_t n, uint32_t* tmp) {
     const int64_t nb = zu_blocks(n);
     hipLaunchKernelGGL(k_zip_scan_u32, dim3((unsigned)nb), dim3(kZsThreads), 0, st, data, n, tmp);
     hipError_t e = hipGetLastError();
@@ -207,13 +203,18 @@ static hipError_t zip_scan_u32(hipStream_t st, uint32_t* data, int64_t n, uint32
     hipLaunchKernelGGL(k_zip_add_u32, dim3((unsigned)nb), dim3(kZsThreads), 0, st, data, n, tmp);
     return hipGetLastError();
 }
-static size_t zip_scan_u32_tmp(int64_t n) {
+size_t zip_scan_u32_tmp(int64_t n) {
     size_t total = 0;
     for (int64_t nb = zu_blocks(std::max<int64_t>(n, 1));; nb = zu_blocks(nb)) {
         total += (size_t)nb;
         if (nb <= 1) break;
     }
     return total;
+}
+
+hipError_t launch_zip_hist64(hipStream_t st, const uint64_t* keys, int64_t n, int pass, uint32_t* hist, int nblocks) {
+    hipLaunchKernelGGL(k_zip_hist<uint64_t>, dim3(nblocks), dim3(kZsThreads), 0, st, keys, n, pass, hist, nblocks);
+    return hipGetLastError();
 }
 
 template <typename X>

@@ -42,6 +42,13 @@ constexpr int kZipDigits = 1 << kZipDigitBits;
 // Digit `pass` (0 = least significant) of a key.
 SKML_ZIP_HD int zip_digit(uint64_t key, int pass) { return (int)((key >> (kZipDigitBits * pass)) & (kZipDigits - 1)); }
 
+// The sort passes' shape: a workgroup of kZsThreads scatters its tile of kZsTile keys in steps of
+// kZsRows rows of kZsThreads keys, a thread one key of each row.
+constexpr int kZsThreads = 256;
+constexpr int kZsWaves = kZsThreads / 64;
+constexpr int kZsTile = kZsThreads * 32;  // keys per workgroup of a sort pass
+constexpr int kZsRows = 4;
+
 // splitIndex[j] of a round; idx == nullptr is round 1's identity.
 SKML_ZIP_HD int64_t zip_split_at(const int32_t* idx, int64_t j) { return idx ? (int64_t)idx[j] : j; }
 

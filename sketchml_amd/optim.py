@@ -85,12 +85,13 @@ class GradientDescent:
         self.batch = 0
         self.batchNum = float(int(math.ceil(1.0 / batchSpRatio)))  # GradientDescent.scala:21
 
-    def miniBatchGradientDescent(self, weight: torch.Tensor, dataSet, loss):
+    def miniBatchGradientDescent(self, weight: torch.Tensor, dataSet, loss, sequentialLoss: bool = False):
         """GradientDescent.scala:23-51: (grad, batchSize, objLoss, regLoss) of the next
         (size * batchSpRatio).toInt instances of dataSet.loopingRead.  grad is toAuto's choice, a
         DenseDoubleGradient or a SparseDoubleGradient of float64 device tensors, scaled by
         1.0 / batchSize and regularised.  objLoss is a fixed-shape device sum of the per-instance
-        losses, which stay in self.lastLoss for a caller who wants the sequential sum."""
+        losses, which stay in self.lastLoss; with sequentialLoss it is their sum in batch order
+        (skml_glm_seq_sum), the reference's `objLoss += ...` bit for bit given the losses."""
         batchSize = int(dataSet.size * self.batchSpRatio)
         if batchSize == 0 or self.batchSpRatio > 1:
             raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
@@ -107,8 +108,12 @@ class GradientDescent:
             grad = SparseDoubleGradient(self.dim, keys, vals)
         finish_gradient(grad, 1.0 / batchSize, loss, weight)
         regLoss = float(loss.getReg(weight))
+        objLoss = out["objLoss"]
+        if sequentialLoss:
+            from .validation import seq_sum
+            objLoss = seq_sum(out["loss"])
         self.nextBatch()
-        return grad, batchSize, out["objLoss"], regLoss
+        return grad, batchSize, objLoss, regLoss
 
     def nextBatch(self) -> None:
         """The counters' step at the end of miniBatchGradientDescent (GradientDescent.scala:48-49)."""

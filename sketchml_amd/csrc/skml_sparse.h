@@ -1,4 +1,4 @@
-// skml_sparse.h -- sparse-path device structures and launchers shared by skml_sparse_api.cpp and
+// skml_sparse.h -- sparse-path device structures and launchers shared by skml_sparse_*.cpp and
 // skml_sparse.hip (SparseVectorCompressor / GroupedMinMaxSketch / DeltaAdaptiveEncoder).
 #pragma once
 #include <hip/hip_runtime.h>

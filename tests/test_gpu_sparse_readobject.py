@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import sparse_wire_fixtures as FX
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +78,22 @@ def test_read_object_rejects_malformed(gpu):
     bad[0:4] = struct.pack(">i", 1000)  # groupNum beyond the supported 64
     with pytest.raises(gpu.SketchMLException):
         gpu.SparsePayload.deserialize(bytes(bad))
+    # every single mutation of tests/sparse_wire_fixtures.py on a 3,000-key stream, then a valid stream
+    # on the same context: no refusal leaves scratch or stream state behind
+    keys, vals, osp = FX.compress(12000, 16, 4, 3, "dups")
+    pl = gpu.encode_sparse(torch.from_numpy(keys).cuda(), torch.from_numpy(vals).cuda(), 16, 4, 3, 0.3, 3, 4)
+    data = pl.serialize()
+    assert data == FX.assemble(osp, 3)[0]
+    for what, mutated in FX.mutations(data):
+        with pytest.raises(gpu.SketchMLException):
+            gpu.SparsePayload.deserialize(mutated, osp.q.values())
+            pytest.fail(f"accepted: {what}")
+    back = gpu.SparsePayload.deserialize(data, osp.q.values())
+    k2, v2 = back.restore()
+    ok, ob = osp.restore()
+    assert np.array_equal(k2.cpu().numpy(), ok)
+    assert np.array_equal(v2.cpu().numpy(), osp.q.values()[ob].astype(np.float32))
+    assert back.serialize() == data
 
 
 def test_decode_without_values_is_refused(gpu):

@@ -1,5 +1,5 @@
 // skml_sparse.h -- sparse-path device structures and launchers shared by skml_sparse_*.cpp and
-// skml_sparse.hip (SparseVectorCompressor / GroupedMinMaxSketch / DeltaAdaptiveEncoder).
+// skml_sparse*.hip (SparseVectorCompressor / GroupedMinMaxSketch / DeltaAdaptiveEncoder).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -57,7 +57,7 @@ constexpr int kDeltaHist = 33;            // bitsNeeded in 1..32
 
 __host__ __device__ inline int64_t sp_tiles(int64_t n, int64_t tile) { return (n + tile - 1) / tile; }
 
-// ---- launchers (skml_sparse.hip) ----
+// ---- launchers: the encode plan (skml_sparse_partition.hip) ----
 // Device-side encode plan (one workgroup each, no host round trip):
 //   edges: the table from `init`, then calGroupEdges / fill from the quantizer header (status on NaN / error);
 //   groups: gstart, cols, tab_off, ncells from the partition totals sizes[G];
@@ -71,6 +71,7 @@ hipError_t launch_sp_finalize(hipStream_t st, SpGroups* gp, const uint64_t* tot)
 // after the end) from the scanned [tiles + 1][2] tile sums.
 hipError_t launch_sp_zero_edges(hipStream_t st, const uint64_t* tile_base, int64_t tiles, const SpGroups* gp,
                                 uint64_t* flag_words, uint64_t* delta_words);
+// ---- launchers: compaction and column scan (skml_sparse_compact.hip) ----
 // DenseDoubleGradient.toSparse: keys/vals of |x| > 1e-8 in index order.  status/ticket zeroed.
 hipError_t launch_compact(hipStream_t st, const float* x, int64_t dim, int32_t* keys, float* vals,
                           uint64_t* status, unsigned* ticket, int64_t* nnz_out);
@@ -83,6 +84,7 @@ hipError_t launch_scan_cols(hipStream_t st, uint64_t* sums, int64_t tiles, int K
 hipError_t launch_scan_cols_small(hipStream_t st, uint64_t* sums, int64_t tiles, int K);
 // The same over K columns of tiles + 1 entries each, column k at sums + k * (tiles + 1).
 hipError_t launch_scan_cols_major(hipStream_t st, uint64_t* sums, int64_t tiles, int K);
+// ---- launchers: group partition (skml_sparse_partition.hip) ----
 // FSketchUtils.partition: per-tile group counts (column-major: group g's column of tiles + 1 at
 // tile_counts + g * (tiles + 1)), then the stable scatter into group order.
 // The grid also zeroes z32[0, n32) and z64[0, n64) (the next passes' counters: no memset launches).
@@ -92,6 +94,7 @@ hipError_t launch_part_count(hipStream_t st, const void* qpayload, int64_t n, co
 hipError_t launch_part_scatter(hipStream_t st, const int32_t* keys, const void* qpayload, int64_t n,
                                const SpGroups* gp, const uint64_t* tile_base, int32_t* gkeys,
                                uint16_t* gbins);
+// ---- launchers: group prep and MinMax insert (skml_sparse_minmax.hip) ----
 // Deltas, bitsNeeded histogram, order check, and the per-bucket pair counts of the bucketed
 // MinMaxSketch.insert (bucket_count: nbuckets u64, zeroed; unused when rows == 0).
 #ifndef SKML_MM_BUCKET_BITS
@@ -154,13 +157,14 @@ hipError_t launch_mm_bucket(hipStream_t st, const void* pairs, const uint64_t* b
 hipError_t launch_sp_qvalues(hipStream_t st, const void* qpayload, double* qv);
 // int32 cells from an exact narrow image of tw (8 or 16) bits: the top code becomes `fill`
 hipError_t launch_widen_cells(hipStream_t st, const void* tn, int tw, int64_t ncells, int32_t fill, int32_t* t32);
+// ---- launchers: DeltaAdaptive writer (skml_sparse_delta.hip) ----
 // DeltaAdaptiveEncoder bit streams: tile sums of (flag bits, delta bits), then the writer.
 hipError_t launch_delta_lens(hipStream_t st, const uint8_t* need, int64_t n, const SpGroups* gp,
                              uint64_t* tile_sums);
 hipError_t launch_delta_write(hipStream_t st, const int32_t* gkeys, const uint8_t* need, int64_t n,
                               SpGroups* gp, const uint64_t* tile_base, uint64_t* flag_words,
                               uint64_t* delta_words);
-// ---- decode (GroupedMinMaxSketch.restore) ----
+// ---- launchers: decode, GroupedMinMaxSketch.restore (skml_sparse_minmax.hip) ----
 hipError_t launch_unary_count(hipStream_t st, const uint64_t* flag_words, int64_t nwords,
                               const SpGroups* gp, uint64_t* tile_sums);
 hipError_t launch_unary_select(hipStream_t st, const uint64_t* flag_words, int64_t nwords,
@@ -215,6 +219,7 @@ hipError_t launch_dec_keys(hipStream_t st, const uint32_t* delta, int64_t n, con
                            unsigned* err, RunBoundsOut rb = RunBoundsOut{nullptr, 0, 0, 0});
 // the narrow (width 8 or 16) image of int32 MinMax tables for k_dec_keys; t32 16-byte aligned
 hipError_t launch_narrow_table(hipStream_t st, const int32_t* t32, int64_t ncells, int width, void* tn);
+// ---- launchers: Gradient.sum (skml_sparse.hip) ----
 // live entries of a restored payload (skml_sparse_decode_sum_f64's toAuto choice)
 // live entries (|quantValues[bin]| > 1e-8) among n narrow bins (bw = 1 or 2 bytes each)
 hipError_t launch_count_live(hipStream_t st, const void* bins, int bw, int64_t n, const double* qv, uint64_t* count);
@@ -269,10 +274,7 @@ struct SpBlobHeader {
     int64_t reserved[7];
 };
 static_assert(sizeof(SpBlobHeader) <= 256, "blob header fits its 256-byte section");
-// One round of pairwise stable merges of sorted runs (Sort.merge order: lower run first on ties).
-// run_start: nruns + 1 device offsets; total = run_start[nruns].
-// run_start: nruns + 1 HOST offsets (passed to the kernels by value); split: (total / 2048 + 2)
-// int64 device scratch (the tile boundaries' merge-path split points)
+// ---- launchers: Sort.merge (skml_sparse.hip) ----
 // Sort.merge in one pass (the regular case: runs ascend strictly, keys distinct and in [0, INT32_MAX)):
 // bounds = G x (kRsRanges + 1) int32 scratch; info->irregular != 0 after the launches means the
 // input was not regular and the caller must run the merge rounds instead.  vkind 0: out = int32
@@ -288,6 +290,9 @@ struct RsInfo {
 hipError_t launch_rs_merge(hipStream_t st, const int32_t* gk, const int32_t* gb, int64_t n, const SpGroups* gp,
                            int32_t* bounds, RsInfo* info, int32_t* keys_out, void* out, int vkind, const double* qv,
                            int nq, bool bounds_ready);  // bounds_ready: the key query wrote bounds and *info
+// One round of pairwise stable merges of sorted runs (Sort.merge order: lower run first on ties).
+// run_start: nruns + 1 HOST offsets (passed to the kernels by value), total = run_start[nruns];
+// split: (total / 2048 + 2) int64 device scratch (the tile boundaries' merge-path split points)
 hipError_t launch_merge_round(hipStream_t st, const int32_t* kin, const int32_t* bin_in, int32_t* kout,
                               int32_t* bout, const int64_t* run_start, int nruns, int64_t total, int64_t* split);
 // values[bins[i]] from the double quantValues LUT (SparseVectorCompressor.java:118-126); a bin
@@ -297,6 +302,7 @@ hipError_t launch_bin_values(hipStream_t st, const int32_t* bins, int64_t n, con
 hipError_t launch_bin_values64(hipStream_t st, const int32_t* bins, int64_t n, const double* qvalues, int B,
                                double* vals, unsigned* err);
 
+// ---- launchers: Huffman encode and decode (skml_sparse_huffman.hip) ----
 // HuffmanEncoder of the MinMaxSketch tables (serialisation): per-group histograms [G][B+1]
 // (symbol B = the fill value), code lengths per tile, and the MSB-first code stream writer
 // (gbit[g] = first bit of group g's stream).  lut[g*(B+1)+sym] = (numBits << 32) | bits.
@@ -308,7 +314,7 @@ hipError_t launch_huff_write(hipStream_t st, const int32_t* table, int64_t ncell
                              const uint64_t* lut, const uint64_t* tile_base, uint64_t* words, int64_t* gbit);
 
 // HuffmanEncoder.decode (readObject side): speculative parallel decoding of the per-group code
-// streams (see skml_sparse.hip).  lut: kHuffLutSize int2 per group row, {value, length} or
+// streams (see skml_sparse_huffman.hip).  lut: kHuffLutSize int2 per group row, {value, length} or
 // {tree node, -1}; nodes: int4 {left, right, value, 0}, left < 0 for a leaf.
 constexpr int kHuffLutBits = 12;
 constexpr int kHuffLutSize = 1 << kHuffLutBits;

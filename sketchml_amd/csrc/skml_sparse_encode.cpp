@@ -2,7 +2,7 @@
 // SparseVectorCompressor.compressSparse (sample/SparseVectorCompressor.java:52-67) over
 // GroupedMinMaxSketch.insert (frequency/GroupedMinMaxSketch.java:51-121), the toSparse compaction
 // in front of it, and the standalone DeltaAdaptiveEncoder (binary/DeltaAdaptiveEncoder.java).  All
-// element work runs in skml_sparse.hip; the host plans launches, owns the per-group table and the
+// element work runs in skml_sparse*.hip; the host plans launches, owns the per-group table and the
 // tiny decisions the reference makes on whole-group statistics (colNum, hash choice, interval choice).
 #include <algorithm>
 #include <cmath>

@@ -1,7 +1,7 @@
 // skml_sparse_restore.cpp -- the restore side of the sparse C ABI (include/skml.h, "Sparse path"):
 // GroupedMinMaxSketch.restore (frequency/GroupedMinMaxSketch.java:123-146), Sort.merge of the
 // groups' runs and SparseVectorCompressor.decompressSparse (sample/SparseVectorCompressor.java:
-// 118-126).  All element work runs in skml_sparse.hip; the host plans the launches.
+// 118-126).  All element work runs in skml_sparse*.hip; the host plans the launches.
 #include <algorithm>
 #include <vector>
 

@@ -2,7 +2,7 @@
 // path"): GroupedMinMaxSketch.writeObject / readObject with the HuffmanEncoder of the MinMaxSketch
 // tables.  The stream's arithmetic (Huffman trees, layout, parse, decode tables) is
 // skml_sparse_wire.hpp; the bytes are assembled and taken apart on the device (skml_wire.hip,
-// skml_sparse.hip), and this file plans those launches.
+// skml_sparse_huffman.hip), and this file plans those launches.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>

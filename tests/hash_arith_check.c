@@ -1,4 +1,4 @@
-/* Host check of the integer shortcuts in the MinMax query's hashes (skml_sparse.hip: div1000,
+/* Host check of the integer shortcuts in the MinMax query's hashes (skml_sparse_minmax.hip: div1000,
  * bkdr3, bkdr_chunks, java_hash_fm's 32-bit branch), with the GPU's 24-bit multiply emulated as
  * the low 32 bits of the product of the operands' low 24 bits.  Exits non-zero on the first
  * mismatch.  Built and run by tests/test_hash_arith.py. */

@@ -2,7 +2,7 @@
 
 C3: a 2^28-dim dense fp32 gradient with 10 % nnz (seed 3), 256 bins, 8 groups, 2 rows,
 colRatio 0.3.  At this size a group holds ~3.4 M keys, its MinMax table ~1 M columns, and the hash
-`% size` runs through the multiply-based modulus (skml_sparse.hip java_hash_fm / DivU32), so the
+`% size` runs through the multiply-based modulus (skml_sparse_minmax.hip java_hash_fm / DivU32), so the
 device path is compared element for element with the C restatement (oracle/skml_oracle.c):
 quantizer header and splits, per group size / colNum / hash ids / MinMax table / DeltaAdaptive
 choice, bit lengths and BitSet words, restore() keys and bins, and the serialised HuffmanEncoder

@@ -1,4 +1,4 @@
-"""The MinMax query's integer shortcuts (skml_sparse.hip: k / 1000 as a double product, BKDR
+"""The MinMax query's integer shortcuts (skml_sparse_minmax.hip: k / 1000 as a double product, BKDR
 chunks with 24-bit multiplies, the 32-bit floor modulus) against the reference's own arithmetic
 (hash/BKDRHash.java:13-21, Int2IntHash's `code % size`), checked on the host: every 32-bit k for
 k / 1000, every key below 2^24 and 4 M random keys per BKDR seed, and modulus edges."""

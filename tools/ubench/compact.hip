@@ -1,5 +1,5 @@
 // Microbenchmark (profiling aid): variants of the toSparse stream compaction (k_compact in
-// skml_sparse.hip) over a 2^28-float, 10 %-dense input, to separate the costs of the ordered
+// skml_sparse_compact.hip) over a 2^28-float, 10 %-dense input, to separate the costs of the ordered
 // ticket, the tile size and the look-back from the streaming read itself.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/ubench/compact tools/ubench/compact.hip
 #include <hip/hip_runtime.h>

@@ -1,8 +1,8 @@
 // Microbenchmark (profiling aid): the bucketed MinMaxSketch insert's scatter (k_mm_scatter in
-// skml_sparse.hip) at the C3 shape (26.8 M keys, 2 rows, colRatio 0.3), against variants that
+// skml_sparse_minmax.hip) at the C3 shape (26.8 M keys, 2 rows, colRatio 0.3), against variants that
 // drop one cost at a time: coalesced instead of scattered pair stores, and no input loads.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I sketchml_amd/csrc -o tools/ubench/scatter tools/ubench/scatter.hip
-#include "../../sketchml_amd/csrc/skml_sparse.hip"
+#include "../../sketchml_amd/csrc/skml_sparse_minmax.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -648,6 +648,16 @@ int skml_sparse_compact_f32(skml_ctx* ctx, const float* dense_dev, int64_t dim, 
 /* The same over the reference's own double[] (DenseDoubleGradient.values): |x| > 1e-8 in double. */
 int skml_sparse_compact_f64(skml_ctx* ctx, const double* dense_dev, int64_t dim, int32_t* keys_dev,
                             double* vals_dev, int64_t* nnz_out);
+/* bf16 / fp16 gradients (no reference call: Java has no 16-bit float), the 16 bits travelling as
+ * uint16_t as in the dense entries.  Widening to float is exact for every bit pattern, so these are
+ * defined as skml_sparse_compact_f32 of the widened buffer: the same ascending keys and, bit for
+ * bit, the same fp32 values (|x| > 1e-8 on the widened value, NaN dropped, +-inf kept).  The kernels
+ * read the 16-bit buffer itself; no fp32 copy of it exists.  dense_dev needs only 2-byte alignment
+ * (16-byte aligned buffers take 16-byte loads).  Synchronising. */
+int skml_sparse_compact_bf16(skml_ctx* ctx, const uint16_t* dense_dev, int64_t dim, int32_t* keys_dev,
+                             float* vals_dev, int64_t* nnz_out);
+int skml_sparse_compact_f16(skml_ctx* ctx, const uint16_t* dense_dev, int64_t dim, int32_t* keys_dev,
+                            float* vals_dev, int64_t* nnz_out);
 
 /* SparseVectorCompressor.compressSparse (sample/SparseVectorCompressor.java:52-67):
  * QuantileQuantizer.quantize(values) then GroupedMinMaxSketch.create(keys, bins)
@@ -664,6 +674,12 @@ int skml_sparse_encode_kv_f64(skml_ctx* ctx, const int32_t* keys_dev, const doub
                               int64_t nnz, const skml_params* params, skml_sparse** out);
 /* SketchGradient.fromSparse after toAuto's compaction: compact + encode_kv. */
 int skml_sparse_encode_f32(skml_ctx* ctx, const float* dense_dev, int64_t dim,
+                           const skml_params* params, skml_sparse** out);
+/* skml_sparse_encode_f32 of the widened bf16 / fp16 buffer (the payload is byte for byte the
+ * same): the 16-bit compaction above, then the fp32 key/value encode. */
+int skml_sparse_encode_bf16(skml_ctx* ctx, const uint16_t* dense_dev, int64_t dim,
+                            const skml_params* params, skml_sparse** out);
+int skml_sparse_encode_f16(skml_ctx* ctx, const uint16_t* dense_dev, int64_t dim,
                            const skml_params* params, skml_sparse** out);
 /* The ml path itself: DenseDoubleGradient.toAuto / toSparse (DenseDoubleGradient.scala:64-95) of a
  * double[] gradient, then SketchGradient.fromSparse on the double values. */
@@ -741,6 +757,20 @@ int skml_sparse_import(skml_ctx* ctx, const void* blob_dev, size_t len, skml_spa
  * no keys (its constructor reads indices.head).  Synchronising. */
 int skml_sparse_decode_sum_f64(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
                                double scale, double* out_dev);
+/* The same sum returned as float, bf16 or fp16 (the 16 bits as uint16_t): exactly
+ * skml_sparse_decode_sum_f64's double sum, x scale included, then cast to float (round to nearest
+ * even) and, for the 16-bit types, that float rounded to nearest even again -- the definition of
+ * skml_dense_decode_sum_bf16.  No partial sum passes through the narrow type: when the sum takes
+ * more than one tile launch (more than 8 payloads, or more than one scratch batch) it is kept in a
+ * dim-double accumulator of the context's scratch and only the last launch writes out_dev.  out_dev
+ * needs only its element's alignment.  Every refusal of the f64 entry is refused the same way
+ * (out_dev's contents are unspecified on error).  Synchronising. */
+int skml_sparse_decode_sum_f32(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
+                               double scale, float* out_dev);
+int skml_sparse_decode_sum_bf16(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
+                                double scale, uint16_t* out_dev);
+int skml_sparse_decode_sum_f16(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
+                               double scale, uint16_t* out_dev);
 /* Host-memory forms of encode_kv / decode (int[] keys and float[] values in JVM arrays). */
 int skml_sparse_encode_kv_host_f32(skml_ctx* ctx, const int32_t* keys_host, const float* vals_host, int64_t nnz,
                                    const skml_params* params, skml_sparse** out);

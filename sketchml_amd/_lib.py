@@ -209,10 +209,14 @@ _SIGS = {
     "skml_delta_encode_host": (C.c_int, [vp, vp, i64, i32p, i32p, i64p, i64p, vp, vp, i64]),
     "skml_delta_decode_host": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp]),
     "skml_sparse_compact_f32": (C.c_int, [vp, vp, i64, vp, vp, i64p]),
+    "skml_sparse_compact_bf16": (C.c_int, [vp, vp, i64, vp, vp, i64p]),
+    "skml_sparse_compact_f16": (C.c_int, [vp, vp, i64, vp, vp, i64p]),
     "skml_sparse_compact_f64": (C.c_int, [vp, vp, i64, vp, vp, i64p]),
     "skml_sparse_encode_kv_f32": (C.c_int, [vp, vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
     "skml_sparse_encode_kv_f64": (C.c_int, [vp, vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
     "skml_sparse_encode_f32": (C.c_int, [vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
+    "skml_sparse_encode_bf16": (C.c_int, [vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
+    "skml_sparse_encode_f16": (C.c_int, [vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
     "skml_sparse_encode_f64": (C.c_int, [vp, vp, i64, C.POINTER(Params), C.POINTER(vp)]),
     "skml_sparse_decode_f32": (C.c_int, [vp, vp, vp, vp]),
     "skml_sparse_decode_f64": (C.c_int, [vp, vp, vp, vp]),
@@ -230,6 +234,9 @@ _SIGS = {
     "skml_sparse_export": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "skml_sparse_import": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(vp)]),
     "skml_sparse_decode_sum_f64": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
+    "skml_sparse_decode_sum_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
+    "skml_sparse_decode_sum_bf16": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
+    "skml_sparse_decode_sum_f16": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
     "skml_delta_encode": (C.c_int, [vp, vp, i64, i32p, i32p, i64p, i64p, vp, vp, i64]),
     "skml_delta_decode": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp]),
     "skml_comm_unique_id": (C.c_int, [u8p]),

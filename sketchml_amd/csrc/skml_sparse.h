@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/skml.h"
+#include "skml_internal.h"
 
 namespace skml {
 
@@ -74,6 +75,11 @@ hipError_t launch_sp_zero_edges(hipStream_t st, const uint64_t* tile_base, int64
 // ---- launchers: compaction and column scan (skml_sparse_compact.hip) ----
 // DenseDoubleGradient.toSparse: keys/vals of |x| > 1e-8 in index order.  status/ticket zeroed.
 hipError_t launch_compact(hipStream_t st, const float* x, int64_t dim, int32_t* keys, float* vals,
+                          uint64_t* status, unsigned* ticket, int64_t* nnz_out);
+// the same over bf16 / fp16 storage read as it is: the fp32 compaction of the widened buffer
+hipError_t launch_compact(hipStream_t st, const bf16_t* x, int64_t dim, int32_t* keys, float* vals,
+                          uint64_t* status, unsigned* ticket, int64_t* nnz_out);
+hipError_t launch_compact(hipStream_t st, const f16_t* x, int64_t dim, int32_t* keys, float* vals,
                           uint64_t* status, unsigned* ticket, int64_t* nnz_out);
 // the same over doubles (DenseDoubleGradient's own values); tiles of kCompactTile / 2
 hipError_t launch_compact64(hipStream_t st, const double* x, int64_t dim, int32_t* keys, double* vals,
@@ -253,6 +259,19 @@ int agg_tile_bits(bool vtiles);
 hipError_t launch_agg_tiles(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, double* out,
                             int from_out, double scale, unsigned* err, bool vtiles, const int32_t* kbase,
                             const uint8_t* bbase, bool any_dense);
+// The last launch of a sum returned as float / bf16 / fp16 (skml_sparse_decode_sum_f32 / _bf16 /
+// _f16): the tile's double sum, x scale, rounded to float and then to the 16-bit type in the store.
+// from_out: the sum continues from the `dim` doubles of `src`, which earlier launch_agg_tiles
+// calls wrote; the narrow type never holds a partial sum.
+hipError_t launch_agg_tiles_f32(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, float* out,
+                                const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                const int32_t* kbase, const uint8_t* bbase, bool any_dense);
+hipError_t launch_agg_tiles_bf16(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 bf16_t* out, const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense);
+hipError_t launch_agg_tiles_f16(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, f16_t* out,
+                                const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                const int32_t* kbase, const uint8_t* bbase, bool any_dense);
 
 // Exported sparse payload: one contiguous device blob (skml_sparse_export / _import, the unit the
 // RCCL all-gather moves).  Offsets are from the blob start, every section 256-byte aligned.

@@ -166,9 +166,33 @@ __device__ __forceinline__ TileWalk tile_walk_xcd(int64_t blk, int64_t nblk, int
     if (nblk % 8 != 0) return tile_walk(blk, nblk, sub, nsub, ntiles);
     return {(blk % 8) * (nblk / 8) * nsub + (blk / 8) * nsub + sub, ntiles, nblk * nsub};
 }
-__global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* __restrict__ pays, int P,
-                                                            int64_t ntiles, int64_t dim, double* __restrict__ out,
-                                                            int from_out, double scale, unsigned* __restrict__ err) {
+// Output types of the sum (skml_sparse_decode_sum_f64 / _f32 / _bf16 / _f16).  The sum itself is
+// always double; a narrow type appears only in the store of a finished tile: the double, x scale,
+// rounded to float and (bf16 / fp16) rounded again, the dense decode-sum's definition, with
+// skml_device.hpp's conversions.  A launch that continues a sum (from_out) reads the doubles of
+// `src`: `out` itself for double, else the accumulator the earlier launches wrote.
+// kAggOutVec: values of one 16-byte store.
+template <typename O>
+constexpr int agg_out_vec() { return 16 / (int)sizeof(O); }
+// v[0..kV) (sums, x scale applied) to out[x..x + kV), out + x 16-byte aligned
+template <typename O, int kV = agg_out_vec<O>()>
+__device__ __forceinline__ void agg_store_vec(O* out, int64_t x, const double (&v)[kV]) {
+    static_assert(!std::is_same<O, double>::value, "the double tiles store their double2 themselves");
+    if constexpr (std::is_same<O, float>::value) {
+        typedef float f32x4_v __attribute__((ext_vector_type(4)));
+        const f32x4_v o = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+        *reinterpret_cast<f32x4_v*>(out + x) = o;
+    } else {
+        const u32x4_v o = {narrow2<O>((float)v[0], (float)v[1]), narrow2<O>((float)v[2], (float)v[3]),
+                           narrow2<O>((float)v[4], (float)v[5]), narrow2<O>((float)v[6], (float)v[7])};
+        *reinterpret_cast<u32x4_v*>(out + x) = o;
+    }
+}
+
+template <typename O>
+__device__ __forceinline__ void agg_tiles_w_body(const AggPayload* __restrict__ pays, int P, int64_t ntiles,
+                                                 int64_t dim, O* out, const double* src, int from_out, double scale,
+                                                 unsigned* __restrict__ err) {
     static_assert(kAggThreads / 64 == kAggPB, "one wave per payload of a batch");
     __shared__ double acc[kAggTile];
     __shared__ uint32_t here[kAggPB][kAggTile / 32];  // presence bits, one bitmap per wave
@@ -207,9 +231,27 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* _
     // zeroing of the LDS sum follows it, so both overlap those loads' latency.
     int64_t prev_k0 = -1, prev_nk = 0;
     auto store_prev = [&]() {
-        if (prev_k0 >= 0)
-            for (int x = threadIdx.x; x < prev_nk; x += kAggThreads)
-                out[prev_k0 + x] = scale == 1.0 ? acc[x] : __dmul_rn(acc[x], scale);
+        if constexpr (std::is_same<O, double>::value) {
+            if (prev_k0 >= 0)
+                for (int x = threadIdx.x; x < prev_nk; x += kAggThreads)
+                    out[prev_k0 + x] = scale == 1.0 ? acc[x] : __dmul_rn(acc[x], scale);
+        } else {
+            if (prev_k0 < 0) return;
+            constexpr int kV = agg_out_vec<O>();
+            O* o = out + prev_k0;
+            static_assert(kAggTile % (kV * kAggThreads) == 0, "whole rounds of 16-byte stores");
+            if (prev_nk == kAggTile && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {  // 16 B per lane
+                for (int x = kV * threadIdx.x; x < kAggTile; x += kV * kAggThreads) {
+                    double v[kV];
+#pragma unroll
+                    for (int i = 0; i < kV; i++) v[i] = scale == 1.0 ? acc[x + i] : __dmul_rn(acc[x + i], scale);
+                    agg_store_vec<O>(o, x, v);
+                }
+            } else {
+                for (int x = threadIdx.x; x < prev_nk; x += kAggThreads)
+                    store_narrow<O>(o, x, (float)(scale == 1.0 ? acc[x] : __dmul_rn(acc[x], scale)));
+            }
+        }
     };
     for (int64_t t = tw.t0; t < tw.t1; t += tw.step) {
         const int64_t k0 = t * kAggTile, nk = std::min<int64_t>(kAggTile, dim - k0);
@@ -281,7 +323,7 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* _
                 store_prev();
                 __syncthreads();
                 for (int x = threadIdx.x; x < kAggTile; x += kAggThreads)
-                    acc[x] = (from_out && x < nk) ? out[k0 + x] : 0.0;
+                    acc[x] = (from_out && x < nk) ? src[k0 + x] : 0.0;
                 __syncthreads();
                 prev_k0 = k0;
                 prev_nk = nk;
@@ -329,6 +371,19 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* _
     __syncthreads();
     store_prev();
     if (bad) atomicOr(err, bad);
+}
+__global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* __restrict__ pays, int P,
+                                                            int64_t ntiles, int64_t dim, double* __restrict__ out,
+                                                            int from_out, double scale, unsigned* __restrict__ err) {
+    agg_tiles_w_body<double>(pays, P, ntiles, dim, out, out, from_out, scale, err);
+}
+// the same sum stored as float / bf16 / fp16, continued from the double accumulator `src`
+template <typename O>
+__global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w_o(const AggPayload* __restrict__ pays, int P,
+                                                              int64_t ntiles, int64_t dim, O* __restrict__ out,
+                                                              const double* __restrict__ src, int from_out,
+                                                              double scale, unsigned* __restrict__ err) {
+    agg_tiles_w_body<O>(pays, P, ntiles, dim, out, src, from_out, scale, err);
 }
 
 // One wave per tile of kAggVTile keys, staged: lane 8p + g of the wave holds the run piece of
@@ -735,9 +790,10 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(4))
 // twice as long, ran 5.7 against 5.0 ms for 8 C3 payloads: 247 VGPRs and half the waves per CU,
 // profiles/ab/r05_agg_rmw1k.txt), PER: elements per lane held in registers (a longer tile takes
 // the rest row by row).  DENSE: some payload of the launch takes the dense form.
-template <int BITS, int WAVES, int PER, bool DENSE>
-__global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
-    const AggPayload* __restrict__ pays, int P, int64_t ntiles, int64_t dim, double* __restrict__ out, int from_out,
+// O / src: agg_tiles_w_body's.
+template <int BITS, int WAVES, int PER, bool DENSE, typename O>
+__device__ __forceinline__ void agg_rmw_body(
+    const AggPayload* __restrict__ pays, int P, int64_t ntiles, int64_t dim, O* out, const double* src, int from_out,
     double scale, unsigned* __restrict__ err, const int32_t* __restrict__ kbase, const uint8_t* __restrict__ bbase) {
     constexpr int kTile = 1 << BITS, kKeys = kTile / 64;  // keys per lane in the stores
     static_assert(PER == 8 || PER == 16, "piece bytes written as 8 or 16");
@@ -824,25 +880,48 @@ __global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
     int64_t prev_k0 = -1, prev_nk = 0;
     auto store_prev = [&](int l) {  // the previous tile's sums, x scale, 1 KB per store instruction
         if (prev_k0 < 0) return;
-        double* o = out + prev_k0;
+        O* o = out + prev_k0;
         const bool whole = prev_nk == kTile && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+        if constexpr (!std::is_same<O, double>::value) {  // kV values per lane and store instruction
+            constexpr int kV = agg_out_vec<O>();
+            static_assert(kTile % (64 * kV) == 0, "whole rows of 16-byte stores: a smaller tile would store nothing");
 #pragma unroll
-        for (int q = 0; q < kTile / 128; q++) {
-            const int x = 128 * q + 2 * l;
-            double2 v = *reinterpret_cast<const double2*>(T + x);
-            if (scale != 1.0) {
-                v.x = __dmul_rn(v.x, scale);
-                v.y = __dmul_rn(v.y, scale);
+            for (int q = 0; q < kTile / (64 * kV); q++) {
+                const int x = 64 * kV * q + kV * l;
+                double v[kV];
+#pragma unroll
+                for (int i = 0; i < kV; i += 2) {
+                    const double2 d = *reinterpret_cast<const double2*>(T + x + i);
+                    v[i] = scale != 1.0 ? __dmul_rn(d.x, scale) : d.x;
+                    v[i + 1] = scale != 1.0 ? __dmul_rn(d.y, scale) : d.y;
+                }
+                if (whole) {
+                    agg_store_vec<O>(o, x, v);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < kV; i++)
+                        if (x + i < prev_nk) store_narrow<O>(o, x + i, (float)v[i]);
+                }
             }
+        } else {
+#pragma unroll
+            for (int q = 0; q < kTile / 128; q++) {
+                const int x = 128 * q + 2 * l;
+                double2 v = *reinterpret_cast<const double2*>(T + x);
+                if (scale != 1.0) {
+                    v.x = __dmul_rn(v.x, scale);
+                    v.y = __dmul_rn(v.y, scale);
+                }
 #ifdef SKML_ABLATE_AGG_STORE  // timing ablation only (no sums written): the sum's stores priced
-            if (v.x == 12345.678) o[x] = v.y;
-            continue;
+                if (v.x == 12345.678) o[x] = v.y;
+                continue;
 #endif
-            if (whole) {
-                *reinterpret_cast<double2*>(o + x) = v;
-            } else {
-                if (x < prev_nk) o[x] = v.x;
-                if (x + 1 < prev_nk) o[x + 1] = v.y;
+                if (whole) {
+                    *reinterpret_cast<double2*>(o + x) = v;
+                } else {
+                    if (x < prev_nk) o[x] = v.x;
+                    if (x + 1 < prev_nk) o[x + 1] = v.y;
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -888,8 +967,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
             double2 v = make_double2(0.0, 0.0);
             if (from_out) {
                 const int x = kKeys * ln + 2 * q;
-                if (x < nk) v.x = out[k0 + x];
-                if (x + 1 < nk) v.y = out[k0 + x + 1];
+                if (x < nk) v.x = src[k0 + x];
+                if (x + 1 < nk) v.y = src[k0 + x + 1];
             }
             *reinterpret_cast<double2*>(T + kKeys * ln + 2 * q) = v;
         }
@@ -963,6 +1042,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
     store_prev(lane);
     if (bad) atomicOr(err, bad);
 }
+template <int BITS, int WAVES, int PER, bool DENSE>
+__global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
+    const AggPayload* __restrict__ pays, int P, int64_t ntiles, int64_t dim, double* __restrict__ out, int from_out,
+    double scale, unsigned* __restrict__ err, const int32_t* __restrict__ kbase, const uint8_t* __restrict__ bbase) {
+    agg_rmw_body<BITS, WAVES, PER, DENSE, double>(pays, P, ntiles, dim, out, out, from_out, scale, err, kbase, bbase);
+}
+template <int BITS, int WAVES, int PER, bool DENSE, typename O>
+__global__ __launch_bounds__(64 * WAVES) void k_agg_rmw_o(
+    const AggPayload* __restrict__ pays, int P, int64_t ntiles, int64_t dim, O* __restrict__ out,
+    const double* __restrict__ src, int from_out, double scale, unsigned* __restrict__ err,
+    const int32_t* __restrict__ kbase, const uint8_t* __restrict__ bbase) {
+    agg_rmw_body<BITS, WAVES, PER, DENSE, O>(pays, P, ntiles, dim, out, src, from_out, scale, err, kbase, bbase);
+}
 
 // The staged wave-tile form is the default for payloads of at most 8 groups and 256 quantValues
 // (the caller launches it 8 payloads at a time); the wave-per-payload tiles take every other shape
@@ -1027,6 +1119,54 @@ hipError_t launch_agg_tiles(hipStream_t st, const AggPayload* pays, int P, int64
     hipLaunchKernelGGL(k_agg_tiles_w, dim3(grid), dim3(kAggThreads), 0, st, pays, P, ntiles, dim, out, from_out, scale,
                        err);
     return hipGetLastError();
+}
+
+// The last launch of a sum returned as float / bf16 / fp16: the default forms of launch_agg_tiles
+// (no A/B forms), continued from the doubles of `src` when from_out.
+template <typename O>
+hipError_t launch_agg_tiles_o(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, O* out,
+                              const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                              const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
+    if (ntiles <= 0) return hipSuccess;
+    if (from_out && !src) return hipErrorInvalidValue;
+    if (vtiles) {
+        if (P < 1 || P > kAggVPayloads) return hipErrorInvalidValue;
+#define SKML_RMW_LAUNCH(DENSE)                                                                                   \
+    do {                                                                                                         \
+        static const int res = resident_blocks(k_agg_rmw_o<kAggVBits, 8, 8, DENSE, O>, kAggThreads);              \
+        const int64_t all = sp_tiles(ntiles, 8);                                                                 \
+        const unsigned grid = (unsigned)(res <= 0 ? all : std::min<int64_t>(all, res));                          \
+        hipLaunchKernelGGL((k_agg_rmw_o<kAggVBits, 8, 8, DENSE, O>), dim3(grid), dim3(kAggThreads), 0, st, pays, \
+                           P, ntiles, dim, out, src, from_out, scale, err, kbase, bbase);                        \
+    } while (0)
+        if (any_dense) SKML_RMW_LAUNCH(true);
+        else SKML_RMW_LAUNCH(false);
+#undef SKML_RMW_LAUNCH
+        return hipGetLastError();
+    }
+    static const int resident = resident_blocks(k_agg_tiles_w_o<O>, kAggThreads);
+    const unsigned grid = (unsigned)(resident <= 0 ? ntiles : std::min<int64_t>(ntiles, resident));
+    hipLaunchKernelGGL(k_agg_tiles_w_o<O>, dim3(grid), dim3(kAggThreads), 0, st, pays, P, ntiles, dim, out, src,
+                       from_out, scale, err);
+    return hipGetLastError();
+}
+hipError_t launch_agg_tiles_f32(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, float* out,
+                                const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
+    return launch_agg_tiles_o<float>(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vtiles, kbase, bbase,
+                                     any_dense);
+}
+hipError_t launch_agg_tiles_bf16(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 bf16_t* out, const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
+    return launch_agg_tiles_o<bf16_t>(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vtiles, kbase, bbase,
+                                      any_dense);
+}
+hipError_t launch_agg_tiles_f16(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, f16_t* out,
+                                const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
+    return launch_agg_tiles_o<f16_t>(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vtiles, kbase, bbase,
+                                     any_dense);
 }
 
 // live entries (|quantValues[bin]| > 1e-8) of a restored payload, for toAuto's dense / sparse choice

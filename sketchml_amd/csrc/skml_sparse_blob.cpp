@@ -3,6 +3,7 @@
 // and Gradient.sum over gathered blobs.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "skml_sparse_host.hpp"
@@ -293,6 +294,10 @@ int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** 
     return SKML_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
 // Gradient.sum over P exported sparse payloads (ml/gradient/Gradient.scala:44-49): out = +0.0,
 // then for p = 0..P-1 in order DenseDoubleGradient.plusBy(payload p .toAuto)
 // (DenseDoubleGradient.scala:38; SketchGradient.toSparse -> SparseDoubleGradient.toAuto), then
@@ -302,8 +307,28 @@ int skml_sparse_import(skml_ctx* c, const void* blob, size_t len, skml_sparse** 
 // restored keys, whose constructor requires them strictly increasing and inside [0, dim)
 // (SparseDoubleGradient.scala:9-14): a key repeated across a payload's groups, a run that does not
 // ascend or a key out of range fails the whole sum with SKML_E_ARG.
-int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
-                               double* out) {
+// O: the type `out` is returned in.  The sum is in double whatever O is: a narrow O is written
+// by the last tile launch alone, and the launches before it (more than 8 payloads in the wave-tile
+// form, or more than one scratch batch) keep the sum in a `dim`-double accumulator of the context's
+// scratch; the double entry continues in `out` itself.
+inline hipError_t launch_agg_last(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, float* out,
+                                  const double* src, int from_out, double scale, unsigned* err, bool vt,
+                                  const int32_t* kb, const uint8_t* bb, bool any_dense) {
+    return launch_agg_tiles_f32(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vt, kb, bb, any_dense);
+}
+inline hipError_t launch_agg_last(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, bf16_t* out,
+                                  const double* src, int from_out, double scale, unsigned* err, bool vt,
+                                  const int32_t* kb, const uint8_t* bb, bool any_dense) {
+    return launch_agg_tiles_bf16(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vt, kb, bb, any_dense);
+}
+inline hipError_t launch_agg_last(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, f16_t* out,
+                                  const double* src, int from_out, double scale, unsigned* err, bool vt,
+                                  const int32_t* kb, const uint8_t* bb, bool any_dense) {
+    return launch_agg_tiles_f16(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vt, kb, bb, any_dense);
+}
+
+template <typename O>
+int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale, O* out) {
     if (!c || !blobs || P < 1 || dim < 0 || dim > (int64_t)INT32_MAX || (dim > 0 && !out) || stride % 256)
         return fail(SKML_E_ARG, "bad sparse decode_sum arguments (P >= 1, 256-byte stride, dim in Java int)");
     HIP_TRY(hipSetDevice(c->device));
@@ -340,6 +365,7 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
     HIP_TRY(hipMemsetAsync(err, 0, sizeof(unsigned), st));
     size_t at = 0;
     bool first = true;
+    double* accd = nullptr;  // a narrow O: the sum between launches
     while (at < todo.size()) {
         size_t end = at, bytes = 0;
         while (end < todo.size() && (end == at || bytes + need_of(todo[end]) <= kBudget)) bytes += need_of(todo[end++]);
@@ -441,8 +467,20 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
             const size_t nc = std::min(chunk, pays.size() - c0);
             bool any_dense = false;
             for (size_t q = c0; q < c0 + nc; q++) any_dense |= pays[q].dense_form != 0;
-            HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, first && c0 == 0 ? 0 : 1,
-                                     last && c0 + nc == pays.size() ? scale : 1.0, err, vt, gk, gbn, any_dense));
+            const int from_out = first && c0 == 0 ? 0 : 1;
+            const bool final_launch = last && c0 + nc == pays.size();
+            if constexpr (std::is_same<O, double>::value) {
+                HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, from_out,
+                                         final_launch ? scale : 1.0, err, vt, gk, gbn, any_dense));
+            } else if (final_launch) {
+                HIP_TRY(launch_agg_last(st, d_pays + c0, (int)nc, ntiles, dim, out, accd, from_out, scale, err, vt, gk,
+                                        gbn, any_dense));
+            } else {
+                if (!accd && !(accd = scratch<double>(c, kSlotAggAcc, (size_t)dim)))
+                    return fail(SKML_E_OOM, "decode_sum accumulator (%lld doubles)", (long long)dim);
+                HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, accd, from_out, 1.0, err, vt, gk, gbn,
+                                         any_dense));
+            }
         }
         HIP_TRY(hipStreamSynchronize(st));  // `pays` (host) and the scratch are reused by the next batch
         first = false;
@@ -457,6 +495,30 @@ int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t
         return fail(SKML_E_ARG, "requirement failed: Indices are not strictly increasing (a key repeated across a "
                                 "payload's groups; SparseDoubleGradient.scala:12)");
     return SKML_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int skml_sparse_decode_sum_f64(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                               double* out) {
+    return decode_sum_any<double>(c, blobs, P, stride, dim, scale, out);
+}
+
+int skml_sparse_decode_sum_f32(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                               float* out) {
+    return decode_sum_any<float>(c, blobs, P, stride, dim, scale, out);
+}
+
+int skml_sparse_decode_sum_bf16(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                                uint16_t* out) {
+    return decode_sum_any<bf16_t>(c, blobs, P, stride, dim, scale, reinterpret_cast<bf16_t*>(out));
+}
+
+int skml_sparse_decode_sum_f16(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                               uint16_t* out) {
+    return decode_sum_any<f16_t>(c, blobs, P, stride, dim, scale, reinterpret_cast<f16_t*>(out));
 }
 
 }  // extern "C"

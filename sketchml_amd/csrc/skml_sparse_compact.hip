@@ -5,12 +5,11 @@
 #include <algorithm>
 
 #include "skml_device.hpp"
+#include "skml_lowp.hpp"
 #include "skml_sparse.h"
 #include "skml_sparse_device.hpp"
 
 namespace skml {
-
-constexpr uint32_t kEpsBelowBits = 0x322BCC77u;  // the largest float <= 1e-8 (Maths.scala:8 EPS)
 
 // A count the host may be polling in coherent host memory (ctx_host_word): a system-scope store,
 // so it is not held in L2.  No release: the host only reads the value, and everything that reads
@@ -71,50 +70,99 @@ constexpr int kCompactStage = 4096;  // kept elements staged in LDS; denser tile
 
 // Element traits: fp32 tiles of 16,384 (64 per thread, 16 float4 slabs), fp64 tiles of 8,192 (32
 // per thread, 8 slabs of two double2): 64 KiB of loads in flight per tile either way.
+// bf16 / fp16 tiles of 16,384 as well (8 slabs of one 16-byte load of 8 values: 32 KiB in flight).
+// kPer: values per thread per slab; reg: a value as the tile holds it in registers (the 16 bits
+// themselves for the 16-bit types, widened only when kept); val: the compacted values' type.
 template <typename T> struct CompactT;
 template <> struct CompactT<float> {
-    static constexpr int kTile = kCompactTile;
+    static constexpr int kTile = kCompactTile, kPer = 4;
+    typedef float reg;
+    typedef float val;
     typedef float v2 __attribute__((ext_vector_type(4)));  // one slab = one 16-byte load
     // Maths.scala:8 EPS: |x| > 1e-8 in double; for a float x that is |x| > RD_f32(1e-8) on the
-    // magnitude bits, NaN excluded (abs bits above +inf's).
-    static __device__ __forceinline__ bool keep(float v) {
-        const uint32_t a = __float_as_uint(v) & 0x7FFFFFFFu;
-        return a > kEpsBelowBits && a <= 0x7F800000u;
-    }
+    // magnitude bits, NaN excluded (abs bits above +inf's): keep_f32_bits, skml_lowp.hpp.
+    static __device__ __forceinline__ bool keep(float v) { return keep_f32_bits(__float_as_uint(v)); }
+    static __device__ __forceinline__ float value(float v) { return v; }
+    static __device__ __forceinline__ float load1(const float* __restrict__ x, int64_t i) { return x[i]; }
 };
 template <> struct CompactT<double> {
-    static constexpr int kTile = kCompactTile / 2;
+    static constexpr int kTile = kCompactTile / 2, kPer = 4;
+    typedef double reg;
+    typedef double val;
     typedef double v2 __attribute__((ext_vector_type(2)));  // one slab = two 16-byte loads
     static __device__ __forceinline__ bool keep(double v) {  // |x| > 1e-8, NaN excluded
         const uint64_t a = (uint64_t)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull;
         return a > 0x3E45798EE2308C3Aull && a <= 0x7FF0000000000000ull;
     }
+    static __device__ __forceinline__ double value(double v) { return v; }
+    static __device__ __forceinline__ double load1(const double* __restrict__ x, int64_t i) { return x[i]; }
 };
+// The 16-bit keep tests equal CompactT<float>::keep of the widened value for every pattern
+// (skml_lowp.hpp, tests/sparse_lowp_check.cpp); widening is exact, so the kept values are the fp32
+// compaction's of the widened buffer bit for bit.
+template <> struct CompactT<bf16_t> {
+    static constexpr int kTile = kCompactTile, kPer = 8;
+    typedef uint16_t reg;
+    typedef float val;
+    typedef u32x4_v v2;  // one slab = one 16-byte load of 8 values
+    static __device__ __forceinline__ bool keep(uint16_t h) { return keep_bf16_bits(h); }
+    static __device__ __forceinline__ float value(uint16_t h) { return __uint_as_float(widen_bf16_bits(h)); }
+    static __device__ __forceinline__ uint16_t load1(const bf16_t* __restrict__ x, int64_t i) { return x[i].bits; }
+};
+template <> struct CompactT<f16_t> {
+    static constexpr int kTile = kCompactTile, kPer = 8;
+    typedef uint16_t reg;
+    typedef float val;
+    typedef u32x4_v v2;
+    static __device__ __forceinline__ bool keep(uint16_t h) { return keep_f16_bits(h); }
+    static __device__ __forceinline__ float value(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+    static __device__ __forceinline__ uint16_t load1(const f16_t* __restrict__ x, int64_t i) { return x[i].bits; }
+};
+// the 8 values of one 16-byte load, in index order (low half of each word first)
+__device__ __forceinline__ void cb_unpack8(const u32x4_v& w, uint16_t* f) {
+    f[0] = (uint16_t)w.x, f[1] = (uint16_t)(w.x >> 16), f[2] = (uint16_t)w.y, f[3] = (uint16_t)(w.y >> 16);
+    f[4] = (uint16_t)w.z, f[5] = (uint16_t)(w.z >> 16), f[6] = (uint16_t)w.w, f[7] = (uint16_t)(w.w >> 16);
+}
 template <typename T>
 constexpr int compact_tile() { return CompactT<T>::kTile; }
 
 template <typename T>
 __global__ __launch_bounds__(kSpThreads) void k_compact(const T* __restrict__ x, int64_t dim,
-                                                        int32_t* __restrict__ keys, T* __restrict__ vals,
+                                                        int32_t* __restrict__ keys,
+                                                        typename CompactT<T>::val* __restrict__ vals,
                                                         uint64_t* status, unsigned* ticket, int64_t ntiles,
                                                         int64_t* nnz_out) {
-    constexpr int kTile = CompactT<T>::kTile;
-    constexpr int kSlabs = kTile / (4 * kSpThreads);  // 4 elements per thread per slab
-    static_assert(kSlabs % 4 == 0 && kSlabs <= 16, "16-bit slab counts, 4 per u64, 64-bit keep mask");
+    constexpr int kTile = CompactT<T>::kTile, kE = CompactT<T>::kPer;
+    constexpr int kSlabs = kTile / (kE * kSpThreads);  // kE elements per thread per slab
+    static_assert(kSlabs % 4 == 0 && kSlabs * kE <= 64, "16-bit slab counts, 4 per u64, 64-bit keep mask");
     typedef typename CompactT<T>::v2 vec;
+    typedef typename CompactT<T>::reg reg;
     __shared__ uint32_t wtot[kSpThreads / 64][kSlabs];  // per-wave kept counts of each slab
     __shared__ int64_t s_tile;
     __shared__ uint64_t s_excl;
     __shared__ int32_t stage_k[kCompactStage];
-    __shared__ T stage_v[kCompactStage];
+    __shared__ typename CompactT<T>::val stage_v[kCompactStage];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (t == 0) s_tile = (int64_t)atomicAdd(ticket, 1u);
     __syncthreads();
     const int64_t tile = s_tile;
     const int64_t base = tile * kTile;
     const int64_t lim = dim - base;
-    T f[kSlabs][4];  // slab j of the tile = elements 4 * (j * 256 + t) .. + 3
-    if (lim >= kTile && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    reg f[kSlabs][kE];  // slab j of the tile = elements kE * (j * 256 + t) .. + kE - 1
+    if constexpr (is_lowp<T>::value) {
+        if (lim >= kTile && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+            const vec* src = reinterpret_cast<const vec*>(x + base);
+#pragma unroll
+            for (int j = 0; j < kSlabs; j++) cb_unpack8(__builtin_nontemporal_load(src + j * kSpThreads + t), f[j]);
+        } else {  // a partial tile, or a pointer with only its element's alignment
+#pragma unroll
+            for (int j = 0; j < kSlabs; j++) {
+                const int64_t e0 = kE * ((int64_t)j * kSpThreads + t);
+#pragma unroll
+                for (int e = 0; e < kE; e++) f[j][e] = e0 + e < lim ? CompactT<T>::load1(x, base + e0 + e) : (reg)0;
+            }
+        }
+    } else if (lim >= kTile && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
         const vec* src = reinterpret_cast<const vec*>(x + base);
         constexpr int kVec = 4 / (16 / (int)sizeof(T) >= 4 ? 4 : 16 / (int)sizeof(T));  // loads per slab
         constexpr int kPer = 4 / kVec;                                                 // elements per load
@@ -138,14 +186,15 @@ __global__ __launch_bounds__(kSpThreads) void k_compact(const T* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < kSlabs; j++)
 #pragma unroll
-        for (int e = 0; e < 4; e++) keep |= CompactT<T>::keep(f[j][e]) ? (1ull << (4 * j + e)) : 0ull;
+        for (int e = 0; e < kE; e++) keep |= CompactT<T>::keep(f[j][e]) ? (1ull << (kE * j + e)) : 0ull;
     // wave-inclusive scans of the per-slab counts, four 16-bit lanes per u64
     uint64_t P[kSlabs / 4];
 #pragma unroll
     for (int k = 0; k < kSlabs / 4; k++) {
         uint64_t v = 0;
 #pragma unroll
-        for (int q = 0; q < 4; q++) v |= (uint64_t)__popcll((keep >> (16 * k + 4 * q)) & 15ull) << (16 * q);
+        for (int q = 0; q < 4; q++)
+            v |= (uint64_t)__popcll((keep >> (kE * (4 * k + q))) & ((1ull << kE) - 1)) << (16 * q);
         P[k] = v;
     }
     uint64_t own[kSlabs / 4];
@@ -201,12 +250,12 @@ __global__ __launch_bounds__(kSpThreads) void k_compact(const T* __restrict__ x,
             const uint32_t incl = (uint32_t)(P[j >> 2] >> (16 * (j & 3))) & 0xFFFFu;
             const uint32_t mine = (uint32_t)(own[j >> 2] >> (16 * (j & 3))) & 0xFFFFu;
             uint32_t pos = slab_pre[j] + incl - mine;
-            const int32_t e0 = (int32_t)(base + 4 * ((int64_t)j * kSpThreads + t));
+            const int32_t e0 = (int32_t)(base + kE * ((int64_t)j * kSpThreads + t));
 #pragma unroll
-            for (int e = 0; e < 4; e++)
-                if ((keep >> (4 * j + e)) & 1ull) {
+            for (int e = 0; e < kE; e++)
+                if ((keep >> (kE * j + e)) & 1ull) {
                     stage_k[pos] = e0 + e;
-                    stage_v[pos] = f[j][e];
+                    stage_v[pos] = CompactT<T>::value(f[j][e]);
                     pos++;
                 }
         }
@@ -222,48 +271,53 @@ __global__ __launch_bounds__(kSpThreads) void k_compact(const T* __restrict__ x,
         const uint64_t incl = (P[j >> 2] >> (16 * (j & 3))) & 0xFFFFull;
         const uint64_t mine = (own[j >> 2] >> (16 * (j & 3))) & 0xFFFFull;
         int64_t pos = out0 + slab_pre[j] + (int64_t)(incl - mine);
-        const int32_t e0 = (int32_t)(base + 4 * ((int64_t)j * kSpThreads + t));
+        const int32_t e0 = (int32_t)(base + kE * ((int64_t)j * kSpThreads + t));
 #pragma unroll
-        for (int e = 0; e < 4; e++)
-            if ((keep >> (4 * j + e)) & 1ull) {
+        for (int e = 0; e < kE; e++)
+            if ((keep >> (kE * j + e)) & 1ull) {
                 keys[pos] = e0 + e;
-                vals[pos] = f[j][e];
+                vals[pos] = CompactT<T>::value(f[j][e]);
                 pos++;
             }
     }
 }
 
-// fp32 compaction over big tiles: kCbSub sub-tiles of 8,192 values per workgroup, processed in
+// fp32 / bf16 / fp16 compaction over big tiles: kCbSub sub-tiles of 8,192 values per workgroup, processed in
 // turn (the next sub-tile's 32 KiB of loads in flight while the current one is ranked), their kept
 // values and in-sub-tile offsets staged in LDS; one decoupled look-back per 65,536 values (a
 // quarter of k_compact's: its prefix frontier, 64 tiles per look-back step, no longer trails the
 // tiles' arrival), then coalesced stores.  A tile keeping more than kCbCap values re-reads its
-// input and stores directly.
-constexpr int kCbSlabs = 8;                              // float4 slabs per thread per sub-tile
-constexpr int kCbSubElems = kCbSlabs * 4 * kSpThreads;  // 8,192 values
+// input and stores directly.  A 16-bit sub-tile is 4 slabs of one 16-byte load of 8 values per
+// thread (16 KiB in flight), held as the 16 bits and widened when staged or stored.
+constexpr int kCbSubElems = 32 * kSpThreads;  // 8,192 values: 32 per thread
 constexpr int kCbSub = 8, kCbTile = kCbSub * kCbSubElems, kCbCap = 8192;
-static_assert(kCbSlabs % 4 == 0, "16-bit slab counts, 4 per u64");
+template <typename X>
+constexpr int cb_slabs() { return kCbSubElems / (CompactT<X>::kPer * kSpThreads); }  // fp32: 8 float4 slabs
+static_assert(cb_slabs<float>() % 4 == 0 && cb_slabs<bf16_t>() % 4 == 0, "16-bit slab counts, 4 per u64");
 
-// keep mask and in-sub-tile ranks of one sub-tile held as f[kCbSlabs][4] (slab j = float4 j * 256 + t)
+// keep mask and in-sub-tile ranks of one sub-tile held as f[kCbSlabs][kE] (slab j = 16-byte load j * 256 + t)
+template <int kCbSlabs>
 struct CbRanks {
     uint32_t keep;
     uint32_t slab_pre[kCbSlabs];  // exclusive start of this thread's kept values of slab j in the sub-tile
     uint32_t total;               // kept values in the sub-tile
 };
-__device__ __forceinline__ void cb_rank(const float (&f)[kCbSlabs][4], uint32_t (*wtot)[kCbSlabs], CbRanks& R) {
+template <typename X, int kCbSlabs = cb_slabs<X>(), int kE = CompactT<X>::kPer>
+__device__ __forceinline__ void cb_rank(const typename CompactT<X>::reg (&f)[kCbSlabs][kE],
+                                        uint32_t (*wtot)[kCbSlabs], CbRanks<kCbSlabs>& R) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     uint32_t keep = 0;
 #pragma unroll
     for (int j = 0; j < kCbSlabs; j++)
 #pragma unroll
-        for (int e = 0; e < 4; e++) keep |= CompactT<float>::keep(f[j][e]) ? (1u << (4 * j + e)) : 0u;
+        for (int e = 0; e < kE; e++) keep |= CompactT<X>::keep(f[j][e]) ? (1u << (kE * j + e)) : 0u;
     constexpr int kW = kCbSlabs / 4;
     uint64_t P[kW], own[kW];
 #pragma unroll
     for (int k = 0; k < kW; k++) {
         uint64_t v = 0;
 #pragma unroll
-        for (int q = 0; q < 4; q++) v |= (uint64_t)__popc((keep >> (16 * k + 4 * q)) & 15u) << (16 * q);
+        for (int q = 0; q < 4; q++) v |= (uint64_t)__popc((keep >> (kE * (4 * k + q))) & ((1u << kE) - 1u)) << (16 * q);
         P[k] = own[k] = v;
     }
 #pragma unroll
@@ -299,10 +353,24 @@ __device__ __forceinline__ void cb_rank(const float (&f)[kCbSlabs][4], uint32_t 
     __syncthreads();  // wtot is reused by the next sub-tile
 }
 
-__device__ __forceinline__ void cb_load(const float* __restrict__ x, int64_t base, int64_t dim,
-                                        float (&f)[kCbSlabs][4]) {
+template <typename X, int kCbSlabs = cb_slabs<X>(), int kE = CompactT<X>::kPer>
+__device__ __forceinline__ void cb_load(const X* __restrict__ x, int64_t base, int64_t dim,
+                                        typename CompactT<X>::reg (&f)[kCbSlabs][kE]) {
     const int t = threadIdx.x;
-    if (base + kCbSubElems <= dim) {
+    if constexpr (is_lowp<X>::value) {
+        if (base + kCbSubElems <= dim) {  // x is 16-byte aligned (the launcher checks), base a multiple of 8
+            const u32x4_v* src = reinterpret_cast<const u32x4_v*>(x + base);
+#pragma unroll
+            for (int j = 0; j < kCbSlabs; j++) cb_unpack8(__builtin_nontemporal_load(src + j * kSpThreads + t), f[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kCbSlabs; j++) {
+                const int64_t e0 = base + kE * ((int64_t)j * kSpThreads + t);
+#pragma unroll
+                for (int e = 0; e < kE; e++) f[j][e] = e0 + e < dim ? CompactT<X>::load1(x, e0 + e) : (uint16_t)0;
+            }
+        }
+    } else if (base + kCbSubElems <= dim) {
         typedef float vec4 __attribute__((ext_vector_type(4)));
         const vec4* src = reinterpret_cast<const vec4*>(x + base);
 #pragma unroll
@@ -328,12 +396,15 @@ __device__ __forceinline__ void cb_load(const float* __restrict__ x, int64_t bas
 // with the grid at what the CUs hold at once (tickets are taken in order by running workgroups and
 // a workgroup waits only on lower tickets, so the look-back always progresses); it measured 10-20
 // us slower per C3 encode (profiles/ab/r06_compact_persist.txt).
-__global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3))) void k_compact_big(const float* __restrict__ x, int64_t dim,
+template <typename X>
+__global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3))) void k_compact_big(const X* __restrict__ x, int64_t dim,
                                                             int32_t* __restrict__ keys, float* __restrict__ vals,
                                                             uint64_t* status, unsigned* ticket, int64_t ntiles,
                                                             int64_t* nnz_out) {
     __shared__ float st_v[kCbCap];
     __shared__ uint16_t st_k[kCbCap];  // offset inside the sub-tile (< 2^14)
+    constexpr int kCbSlabs = cb_slabs<X>(), kE = CompactT<X>::kPer;
+    typedef typename CompactT<X>::reg reg;
     __shared__ uint32_t wtot[kSpThreads / 64][kCbSlabs];
     __shared__ uint32_t sub_pre[kCbSub + 1];
     __shared__ int64_t s_tile;
@@ -344,7 +415,7 @@ __global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3)))
     __syncthreads();
     int64_t tile = s_tile;
     if (tile >= ntiles) return;  // workgroup-uniform
-    float f[kCbSlabs][4], g[kCbSlabs][4];
+    reg f[kCbSlabs][kE], g[kCbSlabs][kE];
     cb_load(x, tile * kCbTile, dim, f);
 #pragma unroll 1
     while (true) {
@@ -352,20 +423,20 @@ __global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3)))
         uint32_t run = 0;
 #pragma unroll 1
         for (int sb = 0; sb < kCbSub; sb++) {
-            float (&cur)[kCbSlabs][4] = f;
+            reg (&cur)[kCbSlabs][kE] = f;
             if (sb + 1 < kCbSub) cb_load(x, base + (int64_t)(sb + 1) * kCbSubElems, dim, g);
-            CbRanks R;
-            cb_rank(cur, wtot, R);
+            CbRanks<kCbSlabs> R;
+            cb_rank<X>(cur, wtot, R);
             if (t == 0) sub_pre[sb] = run;
             if (run + R.total <= (uint32_t)kCbCap) {
 #pragma unroll
                 for (int j = 0; j < kCbSlabs; j++) {
                     uint32_t pos = run + R.slab_pre[j];
-                    const int off0 = 4 * (j * kSpThreads + t);
+                    const int off0 = kE * (j * kSpThreads + t);
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if ((R.keep >> (4 * j + e)) & 1u) {
-                            st_v[pos] = cur[j][e];
+                    for (int e = 0; e < kE; e++)
+                        if ((R.keep >> (kE * j + e)) & 1u) {
+                            st_v[pos] = CompactT<X>::value(cur[j][e]);
                             st_k[pos] = (uint16_t)(off0 + e);
                             pos++;
                         }
@@ -375,7 +446,7 @@ __global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3)))
 #pragma unroll
             for (int j = 0; j < kCbSlabs; j++)
 #pragma unroll
-                for (int e = 0; e < 4; e++) f[j][e] = g[j][e];
+                for (int e = 0; e < kE; e++) f[j][e] = g[j][e];
         }
         const uint32_t tile_total = run;
         // every thread read s_tile before cb_rank's barriers: the next ticket may land there now
@@ -413,17 +484,17 @@ __global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3)))
             for (int sb = 0; sb < kCbSub; sb++) {
                 const int64_t sbase = base + (int64_t)sb * kCbSubElems;
                 cb_load(x, sbase, dim, f);
-                CbRanks R;
-                cb_rank(f, wtot, R);
+                CbRanks<kCbSlabs> R;
+                cb_rank<X>(f, wtot, R);
 #pragma unroll
                 for (int j = 0; j < kCbSlabs; j++) {
                     int64_t pos = out0 + sub_pre[sb] + R.slab_pre[j];
-                    const int64_t e0 = sbase + 4 * ((int64_t)j * kSpThreads + t);
+                    const int64_t e0 = sbase + kE * ((int64_t)j * kSpThreads + t);
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if ((R.keep >> (4 * j + e)) & 1u) {
+                    for (int e = 0; e < kE; e++)
+                        if ((R.keep >> (kE * j + e)) & 1u) {
                             keys[pos] = (int32_t)(e0 + e);
-                            vals[pos] = f[j][e];
+                            vals[pos] = CompactT<X>::value(f[j][e]);
                             pos++;
                         }
                 }
@@ -437,27 +508,41 @@ __global__ __launch_bounds__(kSpThreads) __attribute__((amdgpu_waves_per_eu(3)))
 }
 
 template <typename T>
-hipError_t launch_compact_t(hipStream_t st, const T* x, int64_t dim, int32_t* keys, T* vals, uint64_t* status,
-                            unsigned* ticket, int64_t* nnz_out) {
+hipError_t launch_compact_t(hipStream_t st, const T* x, int64_t dim, int32_t* keys, typename CompactT<T>::val* vals,
+                            uint64_t* status, unsigned* ticket, int64_t* nnz_out) {
     const int64_t tiles = sp_tiles(dim, compact_tile<T>());
     if (tiles <= 0) return hipMemsetAsync(nnz_out, 0, sizeof(int64_t), st);
     hipLaunchKernelGGL(k_compact<T>, dim3((unsigned)tiles), dim3(kSpThreads), 0, st, x, dim, keys, vals, status,
                        ticket, tiles, nnz_out);
     return hipGetLastError();
 }
-hipError_t launch_compact(hipStream_t st, const float* x, int64_t dim, int32_t* keys, float* vals,
-                          uint64_t* status, unsigned* ticket, int64_t* nnz_out) {
+// fp32, bf16 and fp16 input, fp32 values out
+template <typename X>
+hipError_t launch_compact_x(hipStream_t st, const X* x, int64_t dim, int32_t* keys, float* vals, uint64_t* status,
+                            unsigned* ticket, int64_t* nnz_out) {
     if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || dim < kCbTile)  // small or unaligned: the one-tile kernel
-        return launch_compact_t<float>(st, x, dim, keys, vals, status, ticket, nnz_out);
+        return launch_compact_t<X>(st, x, dim, keys, vals, status, ticket, nnz_out);
     const int64_t tiles = sp_tiles(dim, kCbTile);
     int64_t grid = tiles;
     if (SKML_COMPACT_PERSIST) {  // the workgroups the CUs hold at once
-        static const int resident = resident_blocks(k_compact_big, kSpThreads);
+        static const int resident = resident_blocks(k_compact_big<X>, kSpThreads);
         if (resident > 0) grid = std::min<int64_t>(tiles, resident);
     }
-    hipLaunchKernelGGL(k_compact_big, dim3((unsigned)grid), dim3(kSpThreads), 0, st, x, dim, keys, vals, status,
+    hipLaunchKernelGGL(k_compact_big<X>, dim3((unsigned)grid), dim3(kSpThreads), 0, st, x, dim, keys, vals, status,
                        ticket, tiles, nnz_out);
     return hipGetLastError();
+}
+hipError_t launch_compact(hipStream_t st, const float* x, int64_t dim, int32_t* keys, float* vals,
+                          uint64_t* status, unsigned* ticket, int64_t* nnz_out) {
+    return launch_compact_x<float>(st, x, dim, keys, vals, status, ticket, nnz_out);
+}
+hipError_t launch_compact(hipStream_t st, const bf16_t* x, int64_t dim, int32_t* keys, float* vals,
+                          uint64_t* status, unsigned* ticket, int64_t* nnz_out) {
+    return launch_compact_x<bf16_t>(st, x, dim, keys, vals, status, ticket, nnz_out);
+}
+hipError_t launch_compact(hipStream_t st, const f16_t* x, int64_t dim, int32_t* keys, float* vals,
+                          uint64_t* status, unsigned* ticket, int64_t* nnz_out) {
+    return launch_compact_x<f16_t>(st, x, dim, keys, vals, status, ticket, nnz_out);
 }
 hipError_t launch_compact64(hipStream_t st, const double* x, int64_t dim, int32_t* keys, double* vals,
                             uint64_t* status, unsigned* ticket, int64_t* nnz_out) {

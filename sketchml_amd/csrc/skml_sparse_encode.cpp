@@ -251,8 +251,9 @@ int encode_kv(skml_ctx* c, const int32_t* keys, const void* vals, bool f64, int6
 // poll: the count goes to the context's host word and the call returns as soon as it is there,
 // with the kernel's last stores possibly still in flight -- only for callers whose next work
 // runs on the same stream (skml_sparse_encode_*); the public compaction synchronises.
-template <typename T>
-int compact_any(skml_ctx* c, const T* dense, int64_t dim, int32_t* keys, T* vals, int64_t* nnz_out,
+// T: the dense values' type; V: the compacted values' (T itself, or float for bf16 / fp16 storage).
+template <typename T, typename V = T>
+int compact_any(skml_ctx* c, const T* dense, int64_t dim, int32_t* keys, V* vals, int64_t* nnz_out,
                 bool poll = false) {
     if (!c || !nnz_out || dim < 0 || (dim > 0 && (!dense || !keys || !vals)))
         return fail(SKML_E_ARG, "bad compaction arguments");
@@ -274,6 +275,21 @@ int compact_any(skml_ctx* c, const T* dense, int64_t dim, int32_t* keys, T* vals
     return sync_to_host(c, nnz_out, nnz_dev, sizeof(int64_t));
 }
 
+// X: float, or bf16 / fp16 storage read as it is; the compacted values are fp32 either way
+template <typename X>
+int encode_dense_x(skml_ctx* c, const X* dense, int64_t dim, const skml_params* p, skml_sparse** out) {
+    if (!c || !out || dim < 0) return fail(SKML_E_ARG, "bad sparse arguments");
+    if (int e = check_params(p)) return e;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t cap = (size_t)std::max<int64_t>(dim, 1);
+    int32_t* keys = scratch<int32_t>(c, kSlotCKeys, cap);
+    float* vals = scratch<float>(c, kSlotCVals, cap);
+    if (!keys || !vals) return fail(SKML_E_OOM, "compaction output");
+    int64_t nnz = 0;
+    if (int e = compact_any<X, float>(c, dense, dim, keys, vals, &nnz, true)) return e;
+    return encode_kv(c, keys, vals, false, nnz, p, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -286,6 +302,16 @@ int skml_sparse_compact_f32(skml_ctx* c, const float* dense, int64_t dim, int32_
 int skml_sparse_compact_f64(skml_ctx* c, const double* dense, int64_t dim, int32_t* keys, double* vals,
                             int64_t* nnz_out) {
     return compact_any<double>(c, dense, dim, keys, vals, nnz_out);
+}
+
+int skml_sparse_compact_bf16(skml_ctx* c, const uint16_t* dense, int64_t dim, int32_t* keys, float* vals,
+                             int64_t* nnz_out) {
+    return compact_any<bf16_t, float>(c, reinterpret_cast<const bf16_t*>(dense), dim, keys, vals, nnz_out);
+}
+
+int skml_sparse_compact_f16(skml_ctx* c, const uint16_t* dense, int64_t dim, int32_t* keys, float* vals,
+                            int64_t* nnz_out) {
+    return compact_any<f16_t, float>(c, reinterpret_cast<const f16_t*>(dense), dim, keys, vals, nnz_out);
 }
 
 int skml_sparse_encode_kv_f32(skml_ctx* c, const int32_t* keys, const float* vals, int64_t nnz,
@@ -310,16 +336,17 @@ int skml_sparse_encode_kv_f64(skml_ctx* c, const int32_t* keys, const double* va
 
 int skml_sparse_encode_f32(skml_ctx* c, const float* dense, int64_t dim, const skml_params* p,
                            skml_sparse** out) {
-    if (!c || !out || dim < 0) return fail(SKML_E_ARG, "bad sparse arguments");
-    if (int e = check_params(p)) return e;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = (size_t)std::max<int64_t>(dim, 1);
-    int32_t* keys = scratch<int32_t>(c, kSlotCKeys, cap);
-    float* vals = scratch<float>(c, kSlotCVals, cap);
-    if (!keys || !vals) return fail(SKML_E_OOM, "compaction output");
-    int64_t nnz = 0;
-    if (int e = compact_any<float>(c, dense, dim, keys, vals, &nnz, true)) return e;
-    return encode_kv(c, keys, vals, false, nnz, p, out);
+    return encode_dense_x<float>(c, dense, dim, p, out);
+}
+
+int skml_sparse_encode_bf16(skml_ctx* c, const uint16_t* dense, int64_t dim, const skml_params* p,
+                            skml_sparse** out) {
+    return encode_dense_x<bf16_t>(c, reinterpret_cast<const bf16_t*>(dense), dim, p, out);
+}
+
+int skml_sparse_encode_f16(skml_ctx* c, const uint16_t* dense, int64_t dim, const skml_params* p,
+                           skml_sparse** out) {
+    return encode_dense_x<f16_t>(c, reinterpret_cast<const f16_t*>(dense), dim, p, out);
 }
 
 int skml_sparse_encode_f64(skml_ctx* c, const double* dense, int64_t dim, const skml_params* p,

@@ -69,6 +69,7 @@ enum {
     kSlotNarrowTab, // the MinMax query's narrow table image
     kSlotRsMerge,   // one-pass Sort.merge: RsInfo + the runs' key-range bounds
     kSlotLookback,  // the restore's look-back statuses (lengths + deltas in one pass)
+    kSlotAggAcc,    // Gradient.sum returned as float / bf16 / fp16: the double sum between tile launches
     kSlotCount_,
 };
 static_assert(kSlotCount_ <= kScratchSlots, "scratch slots");

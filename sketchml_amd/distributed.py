@@ -125,19 +125,20 @@ def gather_blobs(local: torch.Tensor, stride: int, group=None, exchange: Optiona
 
 
 def exchange_sparse(payload, dim: int, group=None, exchange: Optional[PayloadExchange] = None,
-                    scale: float | None = None):
+                    scale: float | None = None, out_dtype: torch.dtype = torch.float64):
     """One DP step of the ml path on P GPUs (GeneralizedLinearModel.scala:145-156): the sizes are
     all-gathered, every rank exports its compressed sparse gradient straight into a slot of the
     largest size, the slots are all-gathered (RCCL over xGMI), and every rank computes Gradient.sum
     of all P payloads (rank order) and the 1/P average, in double, on its own GPU.
-    Returns (the dense double average, the gathered blobs, stride)."""
+    Returns (the dense double average, the gathered blobs, stride).  out_dtype float32 / bfloat16 /
+    float16 returns that double average rounded once on the device (sparse.decode_sum)."""
     from .sparse import decode_sum as _sparse_decode_sum
     world = dist.get_world_size(group)
     stride = blob_stride(agree_sizes(payload.export_bytes(), group))
     local = torch.empty(stride, dtype=torch.uint8, device=torch.device("cuda", payload.device))
     payload.export(local)
     allb = gather_blobs(local, stride, group, exchange)
-    avg = _sparse_decode_sum(allb, world, stride, dim, 1.0 / world if scale is None else scale)
+    avg = _sparse_decode_sum(allb, world, stride, dim, 1.0 / world if scale is None else scale, dtype=out_dtype)
     return avg, allb, stride
 
 

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .constants import Parallel
-from .context import get_context
+from .context import LOWP_DTYPES, as_device_values, get_context
 from .exceptions import SketchMLException, check
 from .quantization import Quantizer, QuantizationType
 
@@ -182,20 +182,44 @@ class SparsePayload:
 
 
 def decode_sum(blobs: torch.Tensor, nblobs: int, stride: int, dim: int, scale: float = 1.0,
-               out: torch.Tensor | None = None) -> torch.Tensor:
+               out: torch.Tensor | None = None, dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """Gradient.sum (ml/gradient/Gradient.scala:44-49) of `nblobs` exported sparse payloads laid out
     `stride` bytes apart: a float64 dense sum of length dim, payloads added in order (then scaled
     when scale != 1).  skml_sparse_decode_sum_f64.  Like SketchGradient.toSparse's
     SparseDoubleGradient constructor, a payload whose restored keys repeat (a key in two groups)
     or leave [0, dim), or that restores no keys at all (the constructor reads indices.head),
-    raises SketchMLException."""
+    raises SketchMLException.
+
+    The result's type is out.dtype, or `dtype` when out is None: float32, bfloat16 and float16 give
+    the same double sum rounded once to float (and then once to the 16-bit type) as it is stored,
+    with no float64 array in between (skml_sparse_decode_sum_f32 / _bf16 / _f16)."""
     dev = blobs.device
+    dt = out.dtype if out is not None else dtype
+    if dt not in _DECODE_SUM:
+        raise SketchMLException(f"sparse decode_sum: unsupported output dtype {dt}")
     if out is None:
-        out = torch.empty(max(int(dim), 1), dtype=torch.float64, device=dev)
-    check(_lib.lib.skml_sparse_decode_sum_f64(get_context(dev.index).handle, C.c_void_p(blobs.data_ptr()),
-                                              int(nblobs), int(stride), int(dim), float(scale),
-                                              C.c_void_p(out.data_ptr())), "sparse_decode_sum")
+        out = torch.empty(max(int(dim), 1), dtype=dt, device=dev)
+    check(getattr(_lib.lib, _DECODE_SUM[dt])(get_context(dev.index).handle, C.c_void_p(blobs.data_ptr()),
+                                             int(nblobs), int(stride), int(dim), float(scale),
+                                             C.c_void_p(out.data_ptr())), "sparse_decode_sum")
     return out[: int(dim)]
+
+
+_DECODE_SUM = {torch.float64: "skml_sparse_decode_sum_f64", torch.float32: "skml_sparse_decode_sum_f32",
+               torch.bfloat16: "skml_sparse_decode_sum_bf16", torch.float16: "skml_sparse_decode_sum_f16"}
+_ENCODE_DENSE = {torch.float64: "skml_sparse_encode_f64", torch.float32: "skml_sparse_encode_f32",
+                 torch.bfloat16: "skml_sparse_encode_bf16", torch.float16: "skml_sparse_encode_f16"}
+_COMPACT = {torch.float64: "skml_sparse_compact_f64", torch.float32: "skml_sparse_compact_f32",
+            torch.bfloat16: "skml_sparse_compact_bf16", torch.float16: "skml_sparse_compact_f16"}
+
+
+def _dense_values(dense):
+    """A dense gradient on the device in the dtype its entry reads: a torch bfloat16 / float16
+    tensor stays as it is (the compaction widens in registers), float64 stays float64, everything
+    else becomes float32."""
+    if isinstance(dense, torch.Tensor) and dense.dtype in LOWP_DTYPES:
+        return as_device_values(dense)
+    return _as_device(dense, _values_dtype(dense))
 
 
 def _as_device(t, dtype, device=None):
@@ -234,26 +258,30 @@ def encode_sparse(keys, values, bin_num=Quantizer.DEFAULT_BIN_NUM, group_num=8, 
 def encode_dense_as_sparse(dense, bin_num=Quantizer.DEFAULT_BIN_NUM, group_num=8, row_num=2, col_ratio=0.3,
                            seed=0, hash_seed=0, uniform=False) -> SparsePayload:
     """SketchGradient.fromSparse after DenseDoubleGradient.toSparse (|x| > 1e-8), on device; a
-    float64 gradient (DenseDoubleGradient.values itself) is compacted and binned as doubles."""
-    x = _as_device(dense, _values_dtype(dense))
+    float64 gradient (DenseDoubleGradient.values itself) is compacted and binned as doubles.  A
+    bfloat16 / float16 tensor is compacted from its own buffer (skml_sparse_encode_bf16 / _f16): the
+    payload is the one its float32 copy would give."""
+    x = _dense_values(dense)
     dev = x.device.index
     ctx = get_context(dev)
     p = _params(bin_num, group_num, row_num, col_ratio, seed, hash_seed, True, uniform)
     h = C.c_void_p()
-    fn = _lib.lib.skml_sparse_encode_f64 if x.dtype == torch.float64 else _lib.lib.skml_sparse_encode_f32
+    fn = getattr(_lib.lib, _ENCODE_DENSE[x.dtype])
     check(fn(ctx.handle, C.c_void_p(x.data_ptr()), x.numel(), C.byref(p), C.byref(h)), "sparse_encode")
     return SparsePayload(h, dev, int(row_num))
 
 
 def to_sparse(dense):
     """DenseDoubleGradient.countNNZ + toSparse (ml/gradient/DenseDoubleGradient.scala:64-89);
-    float64 input keeps float64 values."""
-    x = _as_device(dense, _values_dtype(dense))
+    float64 input keeps float64 values.  A bfloat16 / float16 tensor is read as it is
+    (skml_sparse_compact_bf16 / _f16) and gives float32 values, those of its float32 copy."""
+    x = _dense_values(dense)
     ctx = get_context(x.device.index)
     keys = torch.empty(max(x.numel(), 1), dtype=torch.int32, device=x.device)
-    vals = torch.empty(max(x.numel(), 1), dtype=x.dtype, device=x.device)
+    vals = torch.empty(max(x.numel(), 1), dtype=torch.float64 if x.dtype == torch.float64 else torch.float32,
+                       device=x.device)
     nnz = C.c_int64()
-    fn = _lib.lib.skml_sparse_compact_f64 if x.dtype == torch.float64 else _lib.lib.skml_sparse_compact_f32
+    fn = getattr(_lib.lib, _COMPACT[x.dtype])
     check(fn(ctx.handle, C.c_void_p(x.data_ptr()), x.numel(),
                                            C.c_void_p(keys.data_ptr()), C.c_void_p(vals.data_ptr()),
                                            C.byref(nnz)), "sparse_compact")

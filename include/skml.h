@@ -130,6 +130,18 @@ int skml_debug_sparse_scratch_fail(int on);
  * that does not ascend, a repeated key, a key outside [0, INT32_MAX)) and the rounds ran instead. */
 int skml_debug_sparse_merge_path(void);
 
+/* Test hook: the scratch budget of one batch of skml_sparse_decode_sum_*, process-wide.  The sum
+ * restores its payloads in batches whose keys, bins and run bounds fit 3 GiB of scratch; a later
+ * batch continues the sum of the earlier ones.  `bytes` > 0 replaces the 3 GiB for the calls that
+ * follow (a value above 3 GiB is taken as 3 GiB: the batch's offsets are 32-bit), so that small
+ * payloads reach the continuation; 0 restores it.  A batch always takes at least one payload.
+ * Returns the previous setting (0: the 3 GiB).  Not part of the codec. */
+int64_t skml_debug_sparse_sum_budget(int64_t bytes);
+
+/* Test hook: how many scratch batches and how many tile launches the calling thread's last
+ * skml_sparse_decode_sum_* made (up to where it stopped, if it failed).  Not part of the codec. */
+int skml_debug_sparse_sum_path(int32_t* batches, int32_t* launches);
+
 /* Test hook: force one of the library's alternative kernel forms, process-wide.  Every form gives
  * the same results (the tests run each one against the oracle); 0 is the library's own choice.
  * Returns the previous value, -1 for an unknown id, or -2 (nothing changed) for a form whose

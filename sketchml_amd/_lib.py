@@ -126,6 +126,8 @@ _SIGS = {
     "skml_debug_leaf_stage": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "skml_debug_sparse_scratch_fail": (C.c_int, [C.c_int]),
     "skml_debug_sparse_merge_path": (C.c_int, []),
+    "skml_debug_sparse_sum_budget": (i64, [i64]),
+    "skml_debug_sparse_sum_path": (C.c_int, [i32p, i32p]),
     "skml_debug_form": (C.c_int, [C.c_int, C.c_int]),
     "skml_build_flags": (C.c_int, []),
     "skml_dense_payload_bytes": (C.c_size_t, [i64, i32]),
@@ -294,6 +296,27 @@ def forced_forms(**values):
     finally:
         for k, v in prev.items():
             lib.skml_debug_form(FORMS[k], v)
+
+
+@contextlib.contextmanager
+def sum_budget(nbytes):
+    """with sum_budget(n): the sparse Gradient.sum's scratch budget per batch is n bytes (0: the
+    library's 3 GiB) for the duration (skml_debug_sparse_sum_budget, process-wide); the previous
+    setting comes back on exit."""
+    prev = lib.skml_debug_sparse_sum_budget(int(nbytes))
+    try:
+        yield
+    finally:
+        lib.skml_debug_sparse_sum_budget(prev)
+
+
+def sum_path():
+    """(scratch batches, tile launches) of this thread's last sparse decode_sum
+    (skml_debug_sparse_sum_path)."""
+    batches, launches = i32(-1), i32(-1)
+    if lib.skml_debug_sparse_sum_path(C.byref(batches), C.byref(launches)) != SKML_OK:
+        raise RuntimeError(last_error())
+    return batches.value, launches.value
 
 
 def last_error() -> str:

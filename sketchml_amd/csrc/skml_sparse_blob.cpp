@@ -345,7 +345,10 @@ int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int
     auto bin_bytes = [&](int p) { return (views[(size_t)p].nnz * bin_width(p) + 15) & ~int64_t{15}; };
     // payloads in batches whose restored keys + bins + run bounds fit the scratch budget; the first
     // batch starts the sum at +0.0, later ones continue from it, the last one applies the scale
-    constexpr size_t kBudget = (size_t)3 << 30;
+    // (plan_sum_batches; kSumBudget unless the test hook skml_debug_sparse_sum_budget set a smaller one)
+    t_sum_batches = t_sum_launches = 0;
+    const int64_t hook = g_sum_budget.load();
+    const size_t budget = hook > 0 ? std::min((size_t)hook, kSumBudget) : kSumBudget;
     auto need_of = [&](int p) {
         return (size_t)key_words(p) * 4 + (size_t)bin_bytes(p) +
                (size_t)views[(size_t)p].g.G * (size_t)(ntiles_max + 1) * 4 + 1024;
@@ -363,12 +366,13 @@ int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int
     uint64_t* live = reinterpret_cast<uint64_t*>(small + 256);
     AggPayload* d_pays = reinterpret_cast<AggPayload*>(small + 1024);
     HIP_TRY(hipMemsetAsync(err, 0, sizeof(unsigned), st));
+    std::vector<size_t> need;
+    for (int p : todo) need.push_back(need_of(p));
     size_t at = 0;
     bool first = true;
     double* accd = nullptr;  // a narrow O: the sum between launches
-    while (at < todo.size()) {
-        size_t end = at, bytes = 0;
-        while (end < todo.size() && (end == at || bytes + need_of(todo[end]) <= kBudget)) bytes += need_of(todo[end++]);
+    for (const size_t end : plan_sum_batches(need, budget)) {
+        t_sum_batches++;
         int max_g = 0, max_nq = 0;
         for (size_t q = at; q < end; q++) {
             max_g = std::max(max_g, (int)views[(size_t)todo[q]].g.G);
@@ -469,6 +473,7 @@ int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int
             for (size_t q = c0; q < c0 + nc; q++) any_dense |= pays[q].dense_form != 0;
             const int from_out = first && c0 == 0 ? 0 : 1;
             const bool final_launch = last && c0 + nc == pays.size();
+            t_sum_launches++;
             if constexpr (std::is_same<O, double>::value) {
                 HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, from_out,
                                          final_launch ? scale : 1.0, err, vt, gk, gbn, any_dense));

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "skml_host.hpp"
+#include "skml_sparse_sum_plan.hpp"
 #include "skml_sparse_wire.hpp"
 
 // =============================================================================================
@@ -103,6 +104,8 @@ int sync_to_host(skml_ctx* c, void* dst, const void* src, size_t bytes);
 int scan_tiles(skml_ctx* c, uint64_t* sums, int64_t tiles, int K, uint64_t* totals);
 extern thread_local int t_merge_path;        // skml_debug_sparse_merge_path
 extern std::atomic<int> g_fail_cellbuf;      // skml_debug_sparse_scratch_fail
+extern std::atomic<int64_t> g_sum_budget;    // skml_debug_sparse_sum_budget: 0 = kSumBudget
+extern thread_local int32_t t_sum_batches, t_sum_launches;  // skml_debug_sparse_sum_path
 
 // A payload under construction.  Until release() hands it to the caller, leaving the scope waits
 // for the streams that may still use its memory (a pooled block must have no pending user) and

@@ -44,6 +44,9 @@ namespace skml {
 thread_local int t_merge_path = 0;
 // skml_debug_sparse_scratch_fail: simulate failed MinMax staging allocations (tests only)
 std::atomic<int> g_fail_cellbuf{0};
+// skml_debug_sparse_sum_budget: Gradient.sum's scratch budget per batch (tests only; 0: kSumBudget)
+std::atomic<int64_t> g_sum_budget{0};
+thread_local int32_t t_sum_batches = 0, t_sum_launches = 0;
 
 // smallest pooled block of `dev` holding `bytes` without wasting more than bytes + 64 MiB
 void* block_get(int dev, size_t bytes, size_t* cap) {
@@ -219,6 +222,15 @@ int skml_debug_sparse_merge_path(void) { return t_merge_path; }
 
 int skml_debug_sparse_scratch_fail(int on) {
     g_fail_cellbuf.store(on ? 1 : 0);
+    return SKML_OK;
+}
+
+int64_t skml_debug_sparse_sum_budget(int64_t bytes) { return g_sum_budget.exchange(bytes > 0 ? bytes : 0); }
+
+int skml_debug_sparse_sum_path(int32_t* batches, int32_t* launches) {
+    if (!batches || !launches) return fail(SKML_E_ARG, "NULL argument");
+    *batches = t_sum_batches;
+    *launches = t_sum_launches;
     return SKML_OK;
 }
 

@@ -541,6 +541,35 @@ int skml_glm_gradient_f64(skml_ctx* ctx, const skml_glm_data* data, int64_t row0
 int skml_glm_gradient_f32(skml_ctx* ctx, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
                           const float* w_dev, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
                           int64_t* nnz_out, double* obj_loss_out);
+/* Dense instances (Parser.parseCSV -> Vectors.dense): x holds rows * dim doubles, row-major and
+ * contiguous, 8-byte aligned, on the device, caller-owned and read-only; label[rows].  Every element
+ * takes part, stored zeros, -0.0, NaN and Inf included (0 * Inf is NaN and is added, as in Java). */
+typedef struct skml_glm_dense_data {
+    int64_t rows, dim;
+    const double* x;
+    const double* label;
+} skml_glm_dense_data;
+/* skml_glm_gradient_* over dense instances: the same contract, outputs, NULL rules, single
+ * synchronisation and stream behaviour, with Maths.dot(DenseVector, DenseVector) (Maths.scala:44-55:
+ * i = 0 .. dim - 1 in order) and plusBy(DenseVector, coef_j) (DenseDoubleGradient.scala:44-49).  The bits
+ * are those of skml_glm_gradient_* on a data set that stores every column of every row.  SKML_E_ARG,
+ * with nothing written: as skml_glm_gradient_*, and rows * dim * 8 beyond an int64.  Timed as
+ * SKML_K_GLM_PREDICT and SKML_K_GLM_PLUS_BY.  skml_glm_finish_* serves the gradient unchanged. */
+int skml_glm_gradient_dense_f64(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                int32_t loss_kind, const double* w_dev, double* pre_out, double* coef_out, double* loss_out,
+                                double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_f32(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                int32_t loss_kind, const float* w_dev, double* pre_out, double* coef_out, double* loss_out,
+                                double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+/* The shape constants of the dense kernels (csrc/skml_glm_dense.hpp), for the tests and the benchmark
+ * that place their shapes around them; -1 for any other `which`. */
+#define SKML_GLM_DENSE_C 0            /* columns per tile of the row dot */
+#define SKML_GLM_DENSE_STRIDE 1       /* doubles between two columns of the LDS slab */
+#define SKML_GLM_DENSE_U 2            /* rows in flight of the column sum */
+#define SKML_GLM_DENSE_V 3            /* columns per lane of the column sum */
+#define SKML_GLM_DENSE_ROW_GROUP_AT 4 /* 64-row waves from which two share a workgroup */
+#define SKML_GLM_DENSE_COL_GROUP_AT 5 /* column waves from which four share a workgroup */
+int skml_debug_glm_dense_constant(int which);
 /* grad.timesBy(times), then the regulariser (GradientDescent.scala:53-87), in place, on the form toAuto
  * chose.  SKML_REG_L1 is l1Reg(grad, 0, reg_param) as written: v in [0, theta] -> Math.max(v - 0, 0),
  * v < 0 && v >= -theta -> Math.min(v - 0, 0) (Java's max / min: -0.0 becomes +0.0).  SKML_REG_L2 is
@@ -600,6 +629,13 @@ int skml_glm_validate_f64(skml_ctx* ctx, const skml_glm_data* data, int32_t loss
                           double* pre_out, double* loss_out, skml_valid_result* out);
 int skml_glm_validate_f32(skml_ctx* ctx, const skml_glm_data* data, int32_t loss_kind, const float* w_dev, int32_t flags,
                           double* pre_out, double* loss_out, skml_valid_result* out);
+/* skml_glm_validate_* over dense instances (skml_glm_dense_data above): the same result, flags, NULL
+ * rules, refusals (and rows * dim * 8 beyond an int64) and timing ids; the AUC stage and the sums are
+ * the same code, since they only see pre and loss. */
+int skml_glm_validate_dense_f64(skml_ctx* ctx, const skml_glm_dense_data* data, int32_t loss_kind, const double* w_dev,
+                                int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out);
+int skml_glm_validate_dense_f32(skml_ctx* ctx, const skml_glm_dense_data* data, int32_t loss_kind, const float* w_dev,
+                                int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out);
 /* The AUC stage alone over n scores and labels on the device (n in [1, 2^31 - 1], 8-byte aligned):
  * *pos, *neg, *rank_sum and *nan_scores as above; order_out (optional, n int32 on the device, 4-byte
  * aligned, not overlapping the inputs) receives the sorted permutation: order_out[p] = the instance at

@@ -7,7 +7,7 @@ include/skml.h; this package mirrors the reference's Java surface over that ABI.
 from . import _lib, data, fixed_point, loss, model, optim, validation
 from .compressor import DenseVectorCompressor
 from .constants import Constants, Parallel
-from .data import DataSet, parseCSV, parseDummy, parseLibSVM
+from .data import DataSet, DenseDataSet, parseCSV, parseDense, parseDummy, parseLibSVM
 from .context import Context, alloc_aligned, get_context
 from .exceptions import QuantileSketchException, SketchMLException
 from .loss import L1LogLoss, L2HingeLoss, L2LogLoss, L2SquareLoss, Loss
@@ -21,7 +21,7 @@ from .sparse import (DeltaAdaptiveEncoder, GroupedMinMaxSketch, SparsePayload, S
                      encode_dense_as_sparse, encode_sparse, to_sparse)
 
 __all__ = ["optim", "data", "loss", "model", "validation", "calLossPrecision", "calLossAucPrecision", "ValidationResult", "MLConf",
-           "GeneralizedLinearModel", "LRModel", "SVMModel", "LinearRegModel", "DataSet", "parseLibSVM", "parseDummy", "parseCSV", "Loss", "L1LogLoss", "L2HingeLoss",
+           "GeneralizedLinearModel", "LRModel", "SVMModel", "LinearRegModel", "DataSet", "DenseDataSet", "parseDense", "parseLibSVM", "parseDummy", "parseCSV", "Loss", "L1LogLoss", "L2HingeLoss",
            "L2LogLoss", "L2SquareLoss", "GradientDescent", "Adam", "decode_sum_update", "decode_sum_update_fixed_point", "ZipGradient", "ZipMLQuantizer", "FixedPointGradient", "compress", "decode_sum_fixed_point", "fixed_point", "Constants", "Parallel", "DenseDoubleGradient", "Kind", "SketchGradient", "SparseDoubleGradient", "Context", "DeltaAdaptiveEncoder", "DenseVectorCompressor", "GroupedMinMaxSketch", "SparsePayload",
            "SparseVectorCompressor", "decode_sum", "encode_dense_as_sparse", "encode_sparse", "to_sparse", "QuantileQuantizer", "QuantizationType", "Quantizer", "UniformQuantizer",
            "QuantileSketchException", "SketchMLException", "get_context", "alloc_aligned"]

@@ -98,6 +98,19 @@ class GlmData(C.Structure):
                 ("csc_row", C.c_void_p), ("csc_val", C.c_void_p)]
 
 
+# skml_debug_glm_dense_constant's ids (SKML_GLM_DENSE_* of include/skml.h)
+GLM_DENSE_CONSTANTS = {"C": 0, "STRIDE": 1, "U": 2, "V": 3, "ROW_GROUP_AT": 4, "COL_GROUP_AT": 5}
+
+
+def glm_dense_constant(name: str) -> int:
+    return lib.skml_debug_glm_dense_constant(GLM_DENSE_CONSTANTS[name])
+
+
+class GlmDenseData(C.Structure):
+    """skml_glm_dense_data (include/skml.h): rows * dim doubles, row-major, and the labels on the device."""
+    _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("x", C.c_void_p), ("label", C.c_void_p)]
+
+
 class ValidResult(C.Structure):
     """skml_valid_result (include/skml.h): what one validation pass reads back."""
     _fields_ = [("loss", C.c_double), ("true_pos", C.c_int64), ("true_neg", C.c_int64), ("false_pos", C.c_int64),
@@ -193,6 +206,11 @@ _SIGS = {
     "skml_glm_finish_kv_f64": (C.c_int, [vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, vp, i32]),
     "skml_glm_validate_f64": (C.c_int, [vp, C.POINTER(GlmData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
     "skml_glm_validate_f32": (C.c_int, [vp, C.POINTER(GlmData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_glm_gradient_dense_f64": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_f32": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_validate_dense_f64": (C.c_int, [vp, C.POINTER(GlmDenseData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_glm_validate_dense_f32": (C.c_int, [vp, C.POINTER(GlmDenseData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_debug_glm_dense_constant": (C.c_int, [C.c_int]),
     "skml_auc_rank_sum": (C.c_int, [vp, vp, vp, i64, vp, i64p, i64p, C.POINTER(C.c_uint64), i64p]),
     "skml_glm_seq_sum": (C.c_int, [vp, vp, i64, dblp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),

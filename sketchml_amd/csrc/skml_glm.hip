@@ -18,12 +18,12 @@
 
 #include "skml_device.hpp"
 #include "skml_glm.hpp"
+#include "skml_glm_device.hpp"
 #include "skml_opt.hpp"
 #include "skml_valid.hpp"
 
 namespace skml {
 
-constexpr int kGlmLog = 0, kGlmHinge = 1, kGlmSquare = 2;
 constexpr int kGlmLaneMax = 32;  // a column with at most this many window entries is summed by its own lane
 constexpr int kGlmU = 4;         // chunks of 64 entries the wave form of k_glm_plus_by keeps in flight
 
@@ -63,34 +63,6 @@ __device__ __forceinline__ double ordered_add_lds(double acc, const double* s, i
 }
 
 __device__ __forceinline__ int64_t clamp_ptr(int64_t p, int64_t nnz) { return p < 0 ? 0 : (p > nnz ? nnz : p); }
-
-// loss.loss(pre, y) and loss.grad(pre, y), the branches as Loss.scala writes them.  L1LogLoss and
-// L2LogLoss share their arithmetic.
-template <int LOSS>
-__device__ __forceinline__ void glm_loss(double pre, double y, double& loss, double& grad) {
-    if constexpr (LOSS == kGlmLog) {
-        const double z = pre * y;
-        if (z > 18) {
-            const double e = exp(-z);
-            loss = e;
-            grad = y * e;
-        } else if (z < -18) {
-            loss = -z;
-            grad = y;
-        } else {
-            loss = log(1.0 + exp(-z));
-            grad = y / (1.0 + exp(z));
-        }
-    } else if constexpr (LOSS == kGlmHinge) {
-        const double z = pre * y;
-        loss = z < 1.0 ? 1.0 - z : 0.0;
-        grad = z <= 1.0 ? y : 0.0;
-    } else {
-        const double d = pre - y;
-        loss = (0.5 * d) * d;
-        grad = y - pre;
-    }
-}
 
 // Maths.dot(w, x_row) over the row's entries [s, e) by the row's LPR lanes (sub = the lane's place among
 // them): the gathers and products across lanes, the adds one after the other in stored order from
@@ -167,17 +139,15 @@ __global__ __launch_bounds__(256) void k_glm_predict(skml_glm_data d, GlmWindow 
 
 // The validation pass (ml/util/ValidationUtil.scala:21-31) over every row of the data set: the row dot
 // of k_glm_predict, loss.loss, and the instance's class.  cnt[0 .. 4) += truePos, trueNeg, falsePos,
-// falseNeg and cnt[4] += the NaN scores, as LiveCount counts: a ballot and a popcount per wave, one LDS
-// add per wave, one global atomic per workgroup and counter (integer sums: no order to depend on).
+// falseNeg and cnt[4] += the NaN scores (ValidCount, skml_glm_device.hpp).
 // The column-order arrays of d are not read.
-constexpr int kValidCounters = 5;
 template <typename W, int LOSS, int LPR>
 __global__ __launch_bounds__(256) void k_glm_valid(skml_glm_data d, const W* __restrict__ w, double* __restrict__ pre,
                                                    double* __restrict__ loss, unsigned long long* __restrict__ cnt) {
     __shared__ unsigned long long s_cnt[kValidCounters];
     constexpr int kRows = 256 / LPR;
     const int sub = threadIdx.x % LPR;
-    unsigned long long wave[kValidCounters] = {0, 0, 0, 0, 0};  // wave-uniform
+    ValidCount vc;
     // the trip count is the workgroup's: the cross-lane reads and the ballots need every lane of a wave
     for (int64_t jb = (int64_t)blockIdx.x * kRows; jb < d.rows; jb += (int64_t)gridDim.x * kRows) {
         const int64_t row = jb + threadIdx.x / LPR;
@@ -200,19 +170,9 @@ __global__ __launch_bounds__(256) void k_glm_valid(skml_glm_data d, const W* __r
             cls = valid_class(acc, y);
             nan = acc != acc;
         }
-#pragma unroll
-        for (int k = 0; k < 4; k++) wave[k] += (unsigned long long)__popcll(__ballot(cls == k + 1));
-        wave[4] += (unsigned long long)__popcll(__ballot(nan));
+        vc.add(cls, nan);
     }
-    if (threadIdx.x < kValidCounters) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kValidCounters; k++)
-            if (wave[k]) atomicAdd(&s_cnt[k], wave[k]);
-    }
-    __syncthreads();
-    if (threadIdx.x < kValidCounters && s_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_cnt[threadIdx.x]);
+    vc.finish(s_cnt, cnt);
 }
 
 // acc = 0.0; for i: acc += x[i], the reference's `validLoss += ...` / `objLoss += ...` bit for bit: a

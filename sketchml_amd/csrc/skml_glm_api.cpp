@@ -2,6 +2,7 @@
 // ml/objective/GradientDescent.scala:23-87): argument checks, the context buffer that stands in for
 // the arrays the caller does not keep, the launches of skml_glm.hip and the one read-back of
 // toAuto's count and objLoss.
+#include "skml_glm_dense.hpp"
 #include "skml_host.hpp"
 
 using namespace skml;
@@ -9,6 +10,43 @@ using namespace skml;
 namespace {
 
 constexpr size_t kGlmHead = 256;  // the live counter and objLoss, ahead of the stand-in arrays
+
+// What the sparse and the dense gradient share once their arguments are checked: the workspace that
+// stands in for coef / loss_j, predict(coef, loss), the loss sum, plus_by(coef, counter) and the one
+// read-back of toAuto's count and objLoss after the one synchronisation.
+template <typename Predict, typename PlusBy>
+int gradient_run(skml_ctx* c, int64_t batch, double* coef_out, double* loss_out, int64_t* nnz_out, double* obj_loss_out,
+                 Predict predict, PlusBy plus_by) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bb = (size_t)batch * 8, need = kGlmHead + 2 * bb;
+    if (const int st = reserve(c, c->glm_ws, need, need + need / 4, "the mini-batch gradient's workspace")) return st;
+    char* base = static_cast<char*>(c->glm_ws.p);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(base);
+    double* obj = reinterpret_cast<double*>(base + 8);
+    double* coef = coef_out ? coef_out : reinterpret_cast<double*>(base + kGlmHead);
+    double* loss = loss_out ? loss_out : reinterpret_cast<double*>(base + kGlmHead + bb);
+    unsigned long long* pin = static_cast<unsigned long long*>(ctx_pinned(c, 16));
+    if (!pin) return fail(SKML_E_OOM, "pinned staging of the live count and objLoss");
+
+    HIP_TRY(hipMemsetAsync(cnt, 0, 16, c->stream));
+    {
+        KernelTimer kt(c, SKML_K_GLM_PREDICT);
+        HIP_TRY(predict(coef, loss));
+        HIP_TRY(launch_glm_loss_sum(c->stream, loss, batch, obj));
+    }
+    {
+        KernelTimer kt(c, SKML_K_GLM_PLUS_BY);
+        HIP_TRY(plus_by(coef, cnt));
+    }
+    HIP_TRY(hipMemcpyAsync(pin, cnt, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *nnz_out = (int64_t)pin[0];
+    double o;
+    static_assert(sizeof(o) == sizeof(pin[1]), "objLoss travels as 8 bytes");
+    __builtin_memcpy(&o, &pin[1], sizeof(o));
+    *obj_loss_out = o;
+    return SKML_OK;
+}
 
 int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w, int wide,
                double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
@@ -49,36 +87,56 @@ int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch,
     if (overlap(out[0], out[1]) || overlap(out[0], out[2]) || overlap(out[1], out[2]))
         return fail(SKML_E_ARG, "pre_out, coef_out and loss_out overlap");
 
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t need = kGlmHead + 2 * bb;
-    if (const int st = reserve(c, c->glm_ws, need, need + need / 4, "the mini-batch gradient's workspace")) return st;
-    char* base = static_cast<char*>(c->glm_ws.p);
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(base);
-    double* obj = reinterpret_cast<double*>(base + 8);
-    double* coef = coef_out ? coef_out : reinterpret_cast<double*>(base + kGlmHead);
-    double* loss = loss_out ? loss_out : reinterpret_cast<double*>(base + kGlmHead + bb);
-    unsigned long long* pin = static_cast<unsigned long long*>(ctx_pinned(c, 16));
-    if (!pin) return fail(SKML_E_OOM, "pinned staging of the live count and objLoss");
+    return gradient_run(
+        c, batch, coef_out, loss_out, nnz_out, obj_loss_out,
+        [&](double* coef, double* loss) {
+            return launch_glm_predict(c->stream, *d, row0, batch, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre_out, coef, loss);
+        },
+        [&](const double* coef, unsigned long long* cnt) { return launch_glm_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
+}
 
-    HIP_TRY(hipMemsetAsync(cnt, 0, 16, c->stream));
-    {
-        KernelTimer kt(c, SKML_K_GLM_PREDICT);
-        HIP_TRY(launch_glm_predict(c->stream, *d, row0, batch, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre_out,
-                                   coef, loss));
-        HIP_TRY(launch_glm_loss_sum(c->stream, loss, batch, obj));
+// gradient_x over dense instances: the same checks, then the same gradient_run.
+int gradient_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w,
+                     int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
+                     double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    size_t xb = 0;
+    if (!dense_bytes(d->rows, d->dim, &xb))
+        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
+    if (row0 < 0 || row0 >= d->rows) return fail(SKML_E_ARG, "row0=%lld outside [0, %lld)", (long long)row0, (long long)d->rows);
+    if (batch < 1 || batch > d->rows)
+        return fail(SKML_E_ARG, "batch=%lld outside [1, %lld]: a window wraps at most once", (long long)batch, (long long)d->rows);
+    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
+        loss_kind != SKML_LOSS_L2_SQUARE)
+        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
+    const size_t bb = (size_t)batch * 8, db = (size_t)d->dim * 8;
+    const Range in[] = {{d->x, xb, "x"}, {d->label, (size_t)d->rows * 8, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
+    const Range out[] = {{pre_out, bb, "pre_out"}, {coef_out, bb, "coef_out"}, {loss_out, bb, "loss_out"}};
+    const Range grad{grad_out, db, "grad_out"};
+    if (!d->x || !d->label || !w || !grad_out) return fail(SKML_E_ARG, "x, label, w or grad_out is NULL");
+    if (!nnz_out || !obj_loss_out) return fail(SKML_E_ARG, "nnz_out or obj_loss_out is NULL");
+    for (const Range& r : in)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    for (const Range& r : out)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    if (!aligned8(grad_out)) return fail(SKML_E_ARG, "grad_out must be 8-byte aligned");
+    for (const Range& r : in)
+        if (overlap(grad, r)) return fail(SKML_E_ARG, "grad_out and %s overlap", r.name);
+    for (const Range& r : out) {
+        if (overlap(grad, r)) return fail(SKML_E_ARG, "grad_out and %s overlap", r.name);
+        for (const Range& q : in)
+            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
     }
-    {
-        KernelTimer kt(c, SKML_K_GLM_PLUS_BY);
-        HIP_TRY(launch_glm_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt));
-    }
-    HIP_TRY(hipMemcpyAsync(pin, cnt, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *nnz_out = (int64_t)pin[0];
-    double o;
-    static_assert(sizeof(o) == sizeof(pin[1]), "objLoss travels as 8 bytes");
-    __builtin_memcpy(&o, &pin[1], sizeof(o));
-    *obj_loss_out = o;
-    return SKML_OK;
+    if (overlap(out[0], out[1]) || overlap(out[0], out[2]) || overlap(out[1], out[2]))
+        return fail(SKML_E_ARG, "pre_out, coef_out and loss_out overlap");
+
+    return gradient_run(
+        c, batch, coef_out, loss_out, nnz_out, obj_loss_out,
+        [&](double* coef, double* loss) { return launch_glm_dense_predict(c->stream, *d, row0, batch, loss_kind, w, wide, pre_out, coef, loss); },
+        [&](const double* coef, unsigned long long* cnt) { return launch_glm_dense_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
 }
 
 int finish_x(skml_ctx* c, const int32_t* keys, bool kv, double* vals, int64_t n, int64_t dim, double times, int32_t reg_kind,
@@ -115,6 +173,30 @@ int skml_glm_gradient_f32(skml_ctx* c, const skml_glm_data* data, int64_t row0, 
                           const float* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
                           int64_t* nnz_out, double* obj_loss_out) {
     return gradient_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_glm_gradient_dense_f64(skml_ctx* c, const skml_glm_dense_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                const double* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_dense_x(c, data, row0, batch, loss_kind, w, 1, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_glm_gradient_dense_f32(skml_ctx* c, const skml_glm_dense_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                const float* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_dense_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_debug_glm_dense_constant(int which) {
+    switch (which) {
+        case SKML_GLM_DENSE_C: return kDenseC;
+        case SKML_GLM_DENSE_STRIDE: return kDenseS;
+        case SKML_GLM_DENSE_U: return kDenseU;
+        case SKML_GLM_DENSE_V: return kDenseV;
+        case SKML_GLM_DENSE_ROW_GROUP_AT: return (int)kDenseGroupAt;
+        case SKML_GLM_DENSE_COL_GROUP_AT: return (int)kDenseColGroupAt;
+        default: return -1;
+    }
 }
 
 int skml_glm_finish_dense_f64(skml_ctx* c, double* g, int64_t dim, double times, int32_t reg_kind, double reg_param,

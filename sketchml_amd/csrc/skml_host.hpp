@@ -149,6 +149,13 @@ inline bool overlap(const Range& a, const Range& b) {
 }
 inline bool aligned8(const void* p) { return ((uintptr_t)p) % 8 == 0; }
 constexpr int64_t kJavaIntMax = 0x7FFFFFFFLL;
+// *bytes of the rows * dim doubles of a dense data set; false when rows * dim * 8 does not fit an int64
+inline bool dense_bytes(int64_t rows, int64_t dim, size_t* bytes) {
+    int64_t n;
+    if (__builtin_mul_overflow(rows, dim, &n) || n > INT64_MAX / 8) return false;
+    *bytes = (size_t)n * 8;
+    return true;
+}
 
 inline bool valid_payload_ptr(const void* p) { return p && (((uintptr_t)p) % 256 == 0); }
 

@@ -288,6 +288,13 @@ hipError_t launch_glm_finish(hipStream_t st, const int32_t* keys, double* vals, 
 // scores (zeroed by the caller on the same stream).  d's column-order arrays are not read.
 hipError_t launch_glm_valid(hipStream_t st, const skml_glm_data& d, int loss_kind, const void* w, int wide, int lanes,
                             double* pre, double* loss, unsigned long long* cnt);
+// ---- dense instances (skml_glm_dense.hip): launch_glm_predict / _plus_by / _valid over the row-major x ----
+hipError_t launch_glm_dense_predict(hipStream_t st, const skml_glm_dense_data& d, int64_t row0, int64_t batch, int loss_kind,
+                                    const void* w, int wide, double* pre, double* coef, double* loss);
+hipError_t launch_glm_dense_plus_by(hipStream_t st, const skml_glm_dense_data& d, int64_t row0, int64_t batch,
+                                    const double* coef, double* g, unsigned long long* count);
+hipError_t launch_glm_dense_valid(hipStream_t st, const skml_glm_dense_data& d, int loss_kind, const void* w, int wide,
+                                  double* pre, double* loss, unsigned long long* cnt);
 // *out = ((0.0 + x[0]) + x[1]) + ... + x[n - 1] by one wave
 hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out);
 // Scratch of the key-and-payload sort over n scores; the sorted permutation ends in idx_a.

@@ -56,6 +56,57 @@ double as_double(unsigned long long bits) {
     return v;
 }
 
+// What the sparse and the dense pass share once their arguments are checked: the workspace, the
+// row kernel through launch(pre, loss, counters), the sum, the AUC stage and the one read-back.
+template <typename Launch>
+int validate_run(skml_ctx* c, int64_t rows, const double* label, int32_t flags, double* pre_out, double* loss_out,
+                 skml_valid_result* out, Launch launch) {
+    HIP_TRY(hipSetDevice(c->device));
+    const bool auc = flags & SKML_VALID_AUC;
+    const size_t rb = (size_t)rows * 8;
+    const size_t extra = (pre_out || !auc ? 0 : align_up(rb, 256)) + (loss_out ? 0 : align_up(rb, 256));
+    char* base = nullptr;
+    if (const int st = valid_ws(c, extra, auc ? rows : 0, &base)) return st;
+    unsigned long long* head = reinterpret_cast<unsigned long long*>(base);
+    char* at = base + kHead;
+    double* pre = pre_out;
+    if (!pre && auc) {  // the sort reads the scores
+        pre = reinterpret_cast<double*>(at);
+        at += align_up(rb, 256);
+    }
+    double* loss = loss_out ? loss_out : reinterpret_cast<double*>(at);
+    char* scratch = base + kHead + align_up(extra, 256);
+
+    HIP_TRY(hipMemsetAsync(head, 0, kHead, c->stream));
+    {
+        KernelTimer kt(c, SKML_K_GLM_VALID);
+        HIP_TRY(launch(pre, loss, head));
+    }
+    {
+        KernelTimer kt(c, SKML_K_SEQ_SUM);
+        double* sum = reinterpret_cast<double*>(head + 5);
+        if (flags & SKML_VALID_TREE_SUM) HIP_TRY(launch_glm_loss_sum(c->stream, loss, rows, sum));
+        else HIP_TRY(launch_glm_seq_sum(c->stream, loss, rows, sum));
+    }
+    if (auc)
+        if (const int st = queue_auc(c, pre, label, rows, nullptr, scratch, head)) return st;
+    unsigned long long h[kHeadWords];
+    if (const int st = read_head(c, base, h)) return st;
+    skml_valid_result r;
+    r.loss = as_double(h[5]);
+    r.true_pos = (int64_t)h[0];
+    r.true_neg = (int64_t)h[1];
+    r.false_pos = (int64_t)h[2];
+    r.false_neg = (int64_t)h[3];
+    r.num = rows;
+    r.pos = auc ? (int64_t)h[7] : 0;
+    r.neg = auc ? rows - (int64_t)h[7] : 0;
+    r.rank_sum = auc ? (uint64_t)h[6] : 0;
+    r.nan_scores = (int64_t)h[4];
+    *out = r;
+    return SKML_OK;
+}
+
 int validate_x(skml_ctx* c, const skml_glm_data* d, int32_t loss_kind, const void* w, int wide, int32_t flags, double* pre_out,
                double* loss_out, skml_valid_result* out) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -82,50 +133,40 @@ int validate_x(skml_ctx* c, const skml_glm_data* d, int32_t loss_kind, const voi
             if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
     }
     if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
+    return validate_run(c, d->rows, d->label, flags, pre_out, loss_out, out, [&](double* pre, double* loss, unsigned long long* head) {
+        return launch_glm_valid(c->stream, *d, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre, loss, head);
+    });
+}
 
-    HIP_TRY(hipSetDevice(c->device));
-    const bool auc = flags & SKML_VALID_AUC;
-    const size_t extra = (pre_out || !auc ? 0 : align_up(rb, 256)) + (loss_out ? 0 : align_up(rb, 256));
-    char* base = nullptr;
-    if (const int st = valid_ws(c, extra, auc ? d->rows : 0, &base)) return st;
-    unsigned long long* head = reinterpret_cast<unsigned long long*>(base);
-    char* at = base + kHead;
-    double* pre = pre_out;
-    if (!pre && auc) {  // the sort reads the scores
-        pre = reinterpret_cast<double*>(at);
-        at += align_up(rb, 256);
+int validate_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int32_t loss_kind, const void* w, int wide, int32_t flags,
+                     double* pre_out, double* loss_out, skml_valid_result* out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (!out) return fail(SKML_E_ARG, "out is NULL");
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    size_t xb = 0;
+    if (!dense_bytes(d->rows, d->dim, &xb))
+        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
+    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
+        loss_kind != SKML_LOSS_L2_SQUARE)
+        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
+    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    const size_t rb = (size_t)d->rows * 8;
+    const Range in[] = {{d->x, xb, "x"}, {d->label, rb, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
+    const Range outs[] = {{pre_out, rb, "pre_out"}, {loss_out, rb, "loss_out"}};
+    if (!d->x || !d->label || !w) return fail(SKML_E_ARG, "x, label or w is NULL");
+    for (const Range& r : in)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    for (const Range& r : outs) {
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+        for (const Range& q : in)
+            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
     }
-    double* loss = loss_out ? loss_out : reinterpret_cast<double*>(at);
-    char* scratch = base + kHead + align_up(extra, 256);
-
-    HIP_TRY(hipMemsetAsync(head, 0, kHead, c->stream));
-    {
-        KernelTimer kt(c, SKML_K_GLM_VALID);
-        HIP_TRY(launch_glm_valid(c->stream, *d, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre, loss, head));
-    }
-    {
-        KernelTimer kt(c, SKML_K_SEQ_SUM);
-        double* sum = reinterpret_cast<double*>(head + 5);
-        if (flags & SKML_VALID_TREE_SUM) HIP_TRY(launch_glm_loss_sum(c->stream, loss, d->rows, sum));
-        else HIP_TRY(launch_glm_seq_sum(c->stream, loss, d->rows, sum));
-    }
-    if (auc)
-        if (const int st = queue_auc(c, pre, d->label, d->rows, nullptr, scratch, head)) return st;
-    unsigned long long h[kHeadWords];
-    if (const int st = read_head(c, base, h)) return st;
-    skml_valid_result r;
-    r.loss = as_double(h[5]);
-    r.true_pos = (int64_t)h[0];
-    r.true_neg = (int64_t)h[1];
-    r.false_pos = (int64_t)h[2];
-    r.false_neg = (int64_t)h[3];
-    r.num = d->rows;
-    r.pos = auc ? (int64_t)h[7] : 0;
-    r.neg = auc ? d->rows - (int64_t)h[7] : 0;
-    r.rank_sum = auc ? (uint64_t)h[6] : 0;
-    r.nan_scores = (int64_t)h[4];
-    *out = r;
-    return SKML_OK;
+    if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
+    return validate_run(c, d->rows, d->label, flags, pre_out, loss_out, out, [&](double* pre, double* loss, unsigned long long* head) {
+        return launch_glm_dense_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
+    });
 }
 
 }  // namespace
@@ -140,6 +181,16 @@ int skml_glm_validate_f64(skml_ctx* c, const skml_glm_data* data, int32_t loss_k
 int skml_glm_validate_f32(skml_ctx* c, const skml_glm_data* data, int32_t loss_kind, const float* w, int32_t flags,
                           double* pre_out, double* loss_out, skml_valid_result* out) {
     return validate_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
+}
+
+int skml_glm_validate_dense_f64(skml_ctx* c, const skml_glm_dense_data* data, int32_t loss_kind, const double* w, int32_t flags,
+                                double* pre_out, double* loss_out, skml_valid_result* out) {
+    return validate_dense_x(c, data, loss_kind, w, 1, flags, pre_out, loss_out, out);
+}
+
+int skml_glm_validate_dense_f32(skml_ctx* c, const skml_glm_dense_data* data, int32_t loss_kind, const float* w, int32_t flags,
+                                double* pre_out, double* loss_out, skml_valid_result* out) {
+    return validate_dense_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
 }
 
 int skml_auc_rank_sum(skml_ctx* c, const double* scores, const double* labels, int64_t n, int32_t* order_out, int64_t* pos,

@@ -5,6 +5,8 @@ A DataSet is the CSR of its sparse instances (row_ptr, col, val, label) plus the
 (column, row) order (col_ptr, csc_row, csc_val), which the mini-batch gradient's column kernel walks
 (skml_glm_data, include/skml.h).  A batch of DataSet.loopingRead is a window of consecutive rows, so
 the column order is built once, at first use, with a stable sort; nothing is sorted per batch.
+
+A DenseDataSet holds dense instances (format csv) as one row-major array (skml_glm_dense_data).
 """
 from __future__ import annotations
 
@@ -47,8 +49,25 @@ def parseDummy(line: str, maxDim: int, negY: bool = True):
 
 
 def parseCSV(line: str, maxDim: int, negY: bool = True):
-    """Parser.parseCSV (Parser.scala:45-59) makes dense rows, which the device data set does not hold."""
-    raise SketchMLException("parseCSV: dense instances are not built here (DESIGN.md section 9); use parseLibSVM or parseDummy")
+    """Parser.parseCSV (Parser.scala:45-59) makes dense rows, which the sparse DataSet does not hold:
+    parseDense is the same parser for a DenseDataSet."""
+    raise SketchMLException("parseCSV: a sparse instance from a csv line is not built here; parseDense gives the dense "
+                            "instance (label, values) for a DenseDataSet")
+
+
+def parseDense(line: str, maxDim: int, negY: bool = True):
+    """Parser.parseCSV (Parser.scala:45-59): "y,v,v,..." -> (label, values), a dense instance for a
+    DenseDataSet.  maxDim is not read, as in the reference; the data set checks the length."""
+    splits = line.strip().split(",")
+    return _label(splits[0], negY), [float(t.strip()) for t in splits[1:]]
+
+
+def _device(device):
+    dev = torch.device(device) if device is not None else torch.device(
+        "cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
 
 
 class DataSet:
@@ -60,14 +79,13 @@ class DataSet:
     and builds the column order there.  readIndex is loopingRead's cursor.
     """
 
+    dense = False  # the entries of include/skml.h that serve it: skml_glm_*_f64 / _f32
+
     def __init__(self, dim: int, device=None):
         self.dim = int(dim)
         if not 1 <= self.dim <= JAVA_INT_MAX:
             raise SketchMLException(f"dim={dim} outside [1, 2^31 - 1]")
-        self.device = torch.device(device) if device is not None else torch.device(
-            "cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _device(device)
         self.readIndex = 0
         self._labels: list = []
         self._indices: list = []
@@ -188,4 +206,99 @@ class DataSet:
         d.rows, d.dim, d.nnz = self.rows, self.dim, self.nnz
         for name in ("row_ptr", "col", "val", "label", "col_ptr", "csc_row", "csc_val"):
             setattr(d, name, C.c_void_p(getattr(self, name).data_ptr()).value)
+        return d
+
+
+class DenseDataSet:
+    """A DataSet of dense instances (Parser.parseCSV -> Vectors.dense): rows * dim float64 values,
+    row-major, on the device (skml_glm_dense_data, include/skml.h).  Every element takes part in the
+    dot and in plusBy, stored zeros included, so the bits are those of a DataSet that stores every
+    column; it holds 8 bytes per element instead of 24 and needs no column order.
+
+    DenseDataSet(dim) then add((label, values)) row by row, or fromRows / fromArray.  A row whose
+    length is not dim is refused, where the reference's `require` or an array bound would throw.
+    """
+
+    dense = True  # the entries of include/skml.h that serve it: skml_glm_*_dense_f64 / _f32
+
+    def __init__(self, dim: int, device=None):
+        self.dim = int(dim)
+        if not 1 <= self.dim <= JAVA_INT_MAX:
+            raise SketchMLException(f"dim={dim} outside [1, 2^31 - 1]")
+        self.device = _device(device)
+        self.readIndex = 0
+        self._labels: list = []
+        self._values: list = []
+        self._arrays = None  # (x, label) as given to fromArray
+        self._built = False
+
+    @classmethod
+    def fromRows(cls, rows, dim: int, device=None) -> "DenseDataSet":
+        ds = cls(dim, device)
+        for ins in rows:
+            ds.add(ins)
+        return ds
+
+    @classmethod
+    def fromArray(cls, x, label, dim: int, device=None) -> "DenseDataSet":
+        """x: rows * dim values (rows x dim, or flat and row-major); label: rows values."""
+        ds = cls(dim, device)
+        ds._arrays = (torch.as_tensor(x), torch.as_tensor(label))
+        return ds
+
+    def add(self, ins) -> None:
+        """data += ins, for ins = (label, values); only before the first use."""
+        if self._built or self._arrays is not None:
+            raise SketchMLException("DenseDataSet.add after the first use or on arrays: the rows are fixed")
+        y, values = ins
+        if len(values) != self.dim:
+            raise SketchMLException(f"a dense instance of {len(values)} values in a data set of {self.dim} features")
+        self._labels.append(float(y))
+        self._values.append([float(v) for v in values])
+
+    def __iadd__(self, ins) -> "DenseDataSet":
+        self.add(ins)
+        return self
+
+    @property
+    def size(self) -> int:
+        if self._arrays is not None:
+            return int(self._arrays[1].numel())
+        return len(self._labels)
+
+    take = DataSet.take
+    window_rows = staticmethod(DataSet.window_rows)
+
+    def loopingRead(self):
+        """(label, values) of the next instance, as a host float and list."""
+        r = self.take(1)
+        self._build()
+        return float(self.label[r]), self.x[r * self.dim:(r + 1) * self.dim].tolist()
+
+    def _build(self) -> None:
+        if self._built:
+            return
+        if self._arrays is not None:
+            x, label = self._arrays
+        else:
+            x = torch.tensor(self._values, dtype=torch.float64)
+            label = torch.tensor(self._labels, dtype=torch.float64)
+        x = x.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
+        label = label.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
+        rows = int(label.numel())
+        if rows < 1 or rows > JAVA_INT_MAX:
+            raise SketchMLException(f"{rows} instances: outside [1, 2^31 - 1]")
+        if x.numel() != rows * self.dim:
+            raise SketchMLException(f"{x.numel()} values for {rows} instances of {self.dim} features")
+        self.x, self.label, self.rows = x, label, rows
+        self._arrays = (x, label)
+        self._labels = self._values = None
+        self._built = True
+
+    def glm_data(self) -> _lib.GlmDenseData:
+        """The skml_glm_dense_data of this data set; the tensors stay owned by it."""
+        self._build()
+        d = _lib.GlmDenseData()
+        d.rows, d.dim = self.rows, self.dim
+        d.x, d.label = C.c_void_p(self.x.data_ptr()).value, C.c_void_p(self.label.data_ptr()).value
         return d

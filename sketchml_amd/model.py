@@ -5,7 +5,8 @@ and toAuto, Adam.update and validation.calLossPrecision.
 
 train(), trainOneEpoch, trainOneIteration, computeGradient, aggregateAndUpdate and validate follow
 GeneralizedLinearModel.scala:80-177 line by line with executors = one worker; what Spark aggregates over
-workers is the worker's own value.  The caller passes trainData and validData: the reference's split
+workers is the worker's own value.  The caller passes trainData and validData (each a data.DataSet, or
+a data.DenseDataSet for format csv, which runs the dense entries): the reference's split
 draws scala.util.Random inside a Spark partition and is not reproduced.  workerNum != 1 is refused; the
 multi-rank loop over distributed.py is not built here.
 

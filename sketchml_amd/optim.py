@@ -40,7 +40,7 @@ def _gradient_values(values) -> torch.Tensor:
 
 def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, want_pre: bool = False):
     """skml_glm_gradient_*: the loop of miniBatchGradientDescent over the rows (row0 + j) mod size,
-    j < batch, of a data.DataSet.  Returns a dict of float64 device tensors and two host scalars:
+    j < batch, of a data.DataSet, or of a data.DenseDataSet (skml_glm_gradient_dense_*).  Returns a dict of float64 device tensors and two host scalars:
     grad (dim values, unscaled), coef (-1.0 * loss.grad per instance), loss (per instance), pre (when
     asked for), nnz (toAuto's count of |grad| > 1e-8) and objLoss."""
     dev = weight.device
@@ -52,7 +52,8 @@ def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, w
            "loss": torch.empty(batch, dtype=torch.float64, device=dev),
            "pre": torch.empty(batch, dtype=torch.float64, device=dev) if want_pre else None}
     nnz, obj = C.c_int64(), C.c_double()
-    fn = _lib.lib.skml_glm_gradient_f64 if weight.dtype == torch.float64 else _lib.lib.skml_glm_gradient_f32
+    fn = getattr(_lib.lib, "skml_glm_gradient_" + ("dense_" if dataSet.dense else "") +
+                 ("f64" if weight.dtype == torch.float64 else "f32"))
     check(fn(get_context(dev).handle, C.byref(data), int(row0), int(batch), int(loss.kind), _ptr(weight), _ptr(out["pre"]),
              _ptr(out["coef"]), _ptr(out["loss"]), _ptr(out["grad"]), C.byref(nnz), C.byref(obj)), "glm_gradient")
     out["nnz"], out["objLoss"] = int(nnz.value), float(obj.value)

@@ -99,7 +99,8 @@ def _validate(weights: torch.Tensor, validData, loss, order: str, auc: bool) -> 
     pre = torch.empty(validData.rows, dtype=torch.float64, device=dev)
     per = torch.empty(validData.rows, dtype=torch.float64, device=dev)
     res = _lib.ValidResult()
-    fn = _lib.lib.skml_glm_validate_f64 if weights.dtype == torch.float64 else _lib.lib.skml_glm_validate_f32
+    fn = getattr(_lib.lib, "skml_glm_validate_" + ("dense_" if validData.dense else "") +
+                 ("f64" if weights.dtype == torch.float64 else "f32"))
     check(fn(get_context(dev).handle, C.byref(data), int(loss.kind), _ptr(weights), flags, _ptr(pre), _ptr(per), C.byref(res)),
           "glm_validate")
     extra = {"pre": pre, "loss": per, "nanScores": int(res.nan_scores)}

@@ -109,7 +109,8 @@ int skml_ctx_set_stream(skml_ctx* ctx, void* hip_stream);
 #define SKML_K_SEQ_SUM 11    /* the ordered sum (or, with SKML_VALID_TREE_SUM, the tree sum) */
 #define SKML_K_VALID_SORT 12 /* the keys and one launch per pass of the key-and-payload sort */
 #define SKML_K_VALID_RANK 13 /* the rank sum */
-#define SKML_K_COUNT 14
+#define SKML_K_SPARSE_CHECK 14 /* skml_sparse_decode_sum_step_*: the keys-only check before the fused launch */
+#define SKML_K_COUNT 15
 #define SKML_TIMING_ALL (-1)
 int skml_ctx_set_timing(skml_ctx* ctx, int mask);
 /* Synchronises; total device milliseconds and launch count of kernel `kid` since the reset. */
@@ -819,6 +820,33 @@ int skml_sparse_decode_sum_bf16(skml_ctx* ctx, const void* blobs_dev, int32_t P,
                                 double scale, uint16_t* out_dev);
 int skml_sparse_decode_sum_f16(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
                                double scale, uint16_t* out_dev);
+/* Gradient.sum + timesBy + optimizer.update over P gathered sparse blobs ("Optimiser update" above):
+ * the gradient of element i is the double skml_sparse_decode_sum_f64 would have stored at i (the
+ * sum from +0.0 in payload order, the dense form's |v| > 1e-8 and -0.0 -> +0.0 rules, x scale unless
+ * scale == 1), and it goes into the update of w / m / v where the sum's last tile launch would have
+ * stored it: the dim doubles are neither written nor read back.  The result is bit for bit that of
+ * skml_sparse_decode_sum_f64 followed by skml_opt_step_* with g_fp64 = 1 and scale = 1.
+ * blobs_dev / P / stride / dim / scale and every refusal are skml_sparse_decode_sum_f64's; params,
+ * the state (dim values each, 16-byte aligned, overlapping neither each other nor the blobs, m_dev
+ * and v_dev NULL for SGD) and their checks are skml_dense_decode_sum_step_*'s.
+ * Check first, then update: the sum kernels find a key outside its tile and a key repeated across
+ * a payload's groups in the pass that would write w, so before the one launch that touches the
+ * state a keys-only kernel finds both and the error word is read back.  Whenever the entry returns
+ * anything but SKML_OK, w / m / v hold the bits they held before the call.  (SKML_E_HIP "internal:
+ * check and sum disagree" would be the exception: it reports a defect of the library.)
+ * When the sum takes more than one tile launch (more than 8 payloads, or more than one scratch
+ * batch), the launches before the last keep it in the dim-double accumulator of the context's
+ * scratch, as for skml_sparse_decode_sum_f32.  select: ALL (the default, the reference's
+ * update(DenseDoubleGradient) of Gradient.sum's result) and LIVE are one pass over the payloads
+ * beside the check's pass over the last launch's keys; AUTO costs a second sum pass: the last tile
+ * launch runs once more with the live count in place of its update and is read back before the
+ * update launch.  Synchronising.  The check is timed as SKML_K_SPARSE_CHECK. */
+int skml_sparse_decode_sum_step_f32(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
+                                    double scale, const skml_opt_params* params, float* w_dev, float* m_dev,
+                                    float* v_dev);
+int skml_sparse_decode_sum_step_f64(skml_ctx* ctx, const void* blobs_dev, int32_t P, size_t stride, int64_t dim,
+                                    double scale, const skml_opt_params* params, double* w_dev, double* m_dev,
+                                    double* v_dev);
 /* Host-memory forms of encode_kv / decode (int[] keys and float[] values in JVM arrays). */
 int skml_sparse_encode_kv_host_f32(skml_ctx* ctx, const int32_t* keys_host, const float* vals_host, int64_t nnz,
                                    const skml_params* params, skml_sparse** out);

@@ -88,6 +88,7 @@ SKML_LOSS_L1_LOG, SKML_LOSS_L2_HINGE, SKML_LOSS_L2_LOG, SKML_LOSS_L2_SQUARE = 0,
 SKML_REG_NONE, SKML_REG_L1, SKML_REG_L2 = 0, 1, 2
 SKML_K_GLM_PREDICT, SKML_K_GLM_PLUS_BY, SKML_K_GLM_FINISH = 7, 8, 9
 SKML_K_GLM_VALID, SKML_K_SEQ_SUM, SKML_K_VALID_SORT, SKML_K_VALID_RANK = 10, 11, 12, 13
+SKML_K_SPARSE_CHECK = 14
 SKML_VALID_AUC, SKML_VALID_TREE_SUM = 1, 2
 
 
@@ -257,6 +258,8 @@ _SIGS = {
     "skml_sparse_decode_sum_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
     "skml_sparse_decode_sum_bf16": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
     "skml_sparse_decode_sum_f16": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, vp]),
+    "skml_sparse_decode_sum_step_f32": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
+    "skml_sparse_decode_sum_step_f64": (C.c_int, [vp, vp, i32, C.c_size_t, i64, C.c_double, C.POINTER(OptParams), vp, vp, vp]),
     "skml_delta_encode": (C.c_int, [vp, vp, i64, i32p, i32p, i64p, i64p, vp, vp, i64]),
     "skml_delta_decode": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp]),
     "skml_comm_unique_id": (C.c_int, [u8p]),

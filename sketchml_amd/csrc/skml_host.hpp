@@ -189,4 +189,15 @@ int dense_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t strid
 // *bits: the payloads' width.
 int fixed_sum_headers(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, int* bits);
 
+// ---- what the fused optimiser entries share (skml_optim_api.cpp) ----
+// The checks that need no device: the context, the parameters, the state pointers r[0..3) = w, m, v
+// (16-byte aligned, m and v exactly when Adam), and no two of the nr ranges of `r` overlapping.
+int opt_check_common(skml_ctx* c, const skml_opt_params* p, Range* r, int nr);
+// The step's constants (Adam.scala:54-56's loop invariants, in the reference's double arithmetic).
+OptConsts opt_consts_of(const skml_opt_params& p, int live);
+// SKML_OPT_AUTO: the context's live counter, zeroed on its stream; and the counter read back
+// (synchronises) with toAuto's choice made: *live = 1 for LIVE.
+int opt_counter_zeroed(skml_ctx* c, unsigned long long** out);
+int opt_auto_choice(skml_ctx* c, const unsigned long long* cnt, int64_t dim, int* live);
+
 }  // namespace skml

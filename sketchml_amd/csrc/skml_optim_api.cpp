@@ -8,12 +8,12 @@
 
 using namespace skml;
 
-namespace {
+namespace skml {  // what the fused sparse step (skml_sparse_blob.cpp) shares: declared in skml_host.hpp
 
 // The checks every entry shares, none of which needs a device: the context, the parameters, the
 // state pointers (16-byte aligned, m and v exactly when Adam), and no two of `r` overlapping.
 // r[0..3) are w, m, v; the entry appends its inputs.
-int check_common(skml_ctx* c, const skml_opt_params* p, Range* r, int nr) {
+int opt_check_common(skml_ctx* c, const skml_opt_params* p, Range* r, int nr) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
     if (!p) return fail(SKML_E_ARG, "params is NULL");
     if (p->kind != SKML_OPT_SGD && p->kind != SKML_OPT_ADAM) return fail(SKML_E_ARG, "unknown optimiser kind %d", p->kind);
@@ -35,7 +35,7 @@ int check_common(skml_ctx* c, const skml_opt_params* p, Range* r, int nr) {
 }
 
 // Adam.scala:54-56's loop invariants, in the reference's double arithmetic.
-OptConsts consts_of(const skml_opt_params& p, int live) {
+OptConsts opt_consts_of(const skml_opt_params& p, int live) {
     OptConsts k{};
     k.lr = p.lr;
     k.beta1 = p.beta1;
@@ -52,20 +52,20 @@ OptConsts consts_of(const skml_opt_params& p, int live) {
 
 // DenseDoubleGradient.toAuto's rule (DenseDoubleGradient.scala:92-95): nnz > dim * 2 / 3 in Java
 // int arithmetic (the product wraps for dim > 1,073,741,823; the division truncates toward zero).
-bool auto_dense(int64_t nnz, int64_t dim) {
+static bool auto_dense(int64_t nnz, int64_t dim) {
     const int32_t prod = (int32_t)(uint32_t)((uint64_t)dim * 2u);
     return nnz > (int64_t)(prod / 3);
 }
 
 // The live counter, zeroed on the context's stream.
-int counter_zeroed(skml_ctx* c, unsigned long long** out) {
+int opt_counter_zeroed(skml_ctx* c, unsigned long long** out) {
     if (const int st = reserve(c, c->opt_ws, 256, 256, "the optimiser step's live counter")) return st;
     HIP_TRY(hipMemsetAsync(c->opt_ws.p, 0, sizeof(unsigned long long), c->stream));
     *out = static_cast<unsigned long long*>(c->opt_ws.p);
     return SKML_OK;
 }
 // Reads the counter back (synchronises) and makes AUTO's choice: *live = 1 for LIVE.
-int auto_choice(skml_ctx* c, const unsigned long long* cnt, int64_t dim, int* live) {
+int opt_auto_choice(skml_ctx* c, const unsigned long long* cnt, int64_t dim, int* live) {
     unsigned long long* pin = static_cast<unsigned long long*>(ctx_pinned(c, sizeof(unsigned long long)));
     if (!pin) return fail(SKML_E_OOM, "pinned staging of the live count");
     HIP_TRY(hipMemcpyAsync(pin, cnt, sizeof(*pin), hipMemcpyDeviceToHost, c->stream));
@@ -74,6 +74,10 @@ int auto_choice(skml_ctx* c, const unsigned long long* cnt, int64_t dim, int* li
     return SKML_OK;
 }
 
+}  // namespace skml
+
+namespace {
+
 int decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t stride, int64_t n, double scale,
                       const skml_opt_params* p, int wide, void* w, void* m, void* v) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -81,18 +85,18 @@ int decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t strid
     if (P < 1 || P > 16) return fail(SKML_E_ARG, "P=%d outside [1, 16]", P);
     const size_t sb = (size_t)n * (wide ? 8 : 4);
     Range r[4] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"}, {payloads, (size_t)P * stride, "payloads"}};
-    if (const int st = check_common(c, p, r, 4)) return st;
+    if (const int st = opt_check_common(c, p, r, 4)) return st;
     int common_bits = 0, max_bins = 0;
     if (const int st = dense_sum_headers(c, payloads, P, stride, n, &common_bits, &max_bins)) return st;
     KernelTimer kt(c, SKML_K_DECODE_SUM);
     int live = p->select == SKML_OPT_LIVE;
     if (p->select == SKML_OPT_AUTO) {
         unsigned long long* cnt = nullptr;
-        if (const int st = counter_zeroed(c, &cnt)) return st;
+        if (const int st = opt_counter_zeroed(c, &cnt)) return st;
         HIP_TRY(launch_decode_sum_live(c->stream, payloads, P, stride, n, scale, cnt));
-        if (const int st = auto_choice(c, cnt, n, &live)) return st;
+        if (const int st = opt_auto_choice(c, cnt, n, &live)) return st;
     }
-    HIP_TRY(launch_decode_sum_step(c->stream, payloads, P, stride, n, scale, common_bits, max_bins, consts_of(*p, live), wide,
+    HIP_TRY(launch_decode_sum_step(c->stream, payloads, P, stride, n, scale, common_bits, max_bins, opt_consts_of(*p, live), wide,
                                    w, m, v));
     return SKML_OK;
 }
@@ -109,7 +113,7 @@ int fixed_decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t
     const size_t sb = (size_t)n * (wide ? 8 : 4), before_last = (size_t)(P - 1) * stride;
     Range r[4] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"},
                   {payloads, before_last + skml_fixed_payload_bytes(n, kFxMinBits), "payloads"}};
-    if (const int st = check_common(c, p, r, 4)) return st;
+    if (const int st = opt_check_common(c, p, r, 4)) return st;
     int bits = 0;
     if (const int st = fixed_sum_headers(c, payloads, P, stride, n, &bits)) return st;
     r[3].bytes = before_last + skml_fixed_payload_bytes(n, bits);
@@ -119,11 +123,11 @@ int fixed_decode_sum_step_x(skml_ctx* c, const void* payloads, int32_t P, size_t
     int live = p->select == SKML_OPT_LIVE;
     if (p->select == SKML_OPT_AUTO) {
         unsigned long long* cnt = nullptr;
-        if (const int st = counter_zeroed(c, &cnt)) return st;
+        if (const int st = opt_counter_zeroed(c, &cnt)) return st;
         HIP_TRY(launch_fixed_decode_sum_live(c->stream, payloads, P, stride, n, scale, bits, cnt));
-        if (const int st = auto_choice(c, cnt, n, &live)) return st;
+        if (const int st = opt_auto_choice(c, cnt, n, &live)) return st;
     }
-    HIP_TRY(launch_fixed_decode_sum_step(c->stream, payloads, P, stride, n, scale, bits, consts_of(*p, live), wide, w, m, v));
+    HIP_TRY(launch_fixed_decode_sum_step(c->stream, payloads, P, stride, n, scale, bits, opt_consts_of(*p, live), wide, w, m, v));
     return SKML_OK;
 }
 
@@ -133,18 +137,18 @@ int opt_step_x(skml_ctx* c, const void* g, int32_t g_fp64, int64_t n, double sca
     if (n < 1 || n > 0x7FFFFFFFLL) return fail(SKML_E_ARG, "n=%lld outside [1, 2^31 - 1]", (long long)n);
     const size_t sb = (size_t)n * (wide ? 8 : 4);
     Range r[4] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"}, {g, (size_t)n * (g_fp64 ? 8 : 4), "the gradient"}};
-    if (const int st = check_common(c, p, r, 4)) return st;
+    if (const int st = opt_check_common(c, p, r, 4)) return st;
     if (!g || ((uintptr_t)g) % 16) return fail(SKML_E_ARG, "the gradient must be a 16-byte aligned device pointer");
     HIP_TRY(hipSetDevice(c->device));
     KernelTimer kt(c, SKML_K_DECODE_SUM);
     int live = p->select == SKML_OPT_LIVE;
     if (p->select == SKML_OPT_AUTO) {
         unsigned long long* cnt = nullptr;
-        if (const int st = counter_zeroed(c, &cnt)) return st;
+        if (const int st = opt_counter_zeroed(c, &cnt)) return st;
         HIP_TRY(launch_opt_count(c->stream, g, g_fp64 != 0, n, scale, cnt));
-        if (const int st = auto_choice(c, cnt, n, &live)) return st;
+        if (const int st = opt_auto_choice(c, cnt, n, &live)) return st;
     }
-    HIP_TRY(launch_opt_step(c->stream, g, g_fp64 != 0, n, scale, consts_of(*p, live), wide, w, m, v));
+    HIP_TRY(launch_opt_step(c->stream, g, g_fp64 != 0, n, scale, opt_consts_of(*p, live), wide, w, m, v));
     return SKML_OK;
 }
 
@@ -156,14 +160,14 @@ int opt_step_kv_x(skml_ctx* c, const int32_t* keys, const void* vals, int32_t va
     const size_t sb = (size_t)dim * (wide ? 8 : 4);
     Range r[5] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"}, {keys, (size_t)nnz * 4, "the keys"},
                   {vals, (size_t)nnz * (vals_fp64 ? 8 : 4), "the values"}};
-    if (const int st = check_common(c, p, r, 5)) return st;
+    if (const int st = opt_check_common(c, p, r, 5)) return st;
     if (p->select == SKML_OPT_AUTO)
         return fail(SKML_E_ARG, "SKML_OPT_AUTO does not apply to keys and values: toAuto's choice made them");
     if (nnz > 0 && (!keys || !vals)) return fail(SKML_E_ARG, "keys or values NULL");
     HIP_TRY(hipSetDevice(c->device));
     KernelTimer kt(c, SKML_K_DECODE_SUM);
     HIP_TRY(launch_opt_step_kv(c->stream, keys, vals, vals_fp64 != 0, nnz, dim, scale,
-                               consts_of(*p, p->select == SKML_OPT_LIVE), wide, w, m, v));
+                               opt_consts_of(*p, p->select == SKML_OPT_LIVE), wide, w, m, v));
     return SKML_OK;
 }
 

@@ -272,6 +272,23 @@ hipError_t launch_agg_tiles_bf16(hipStream_t st, const AggPayload* pays, int P, 
 hipError_t launch_agg_tiles_f16(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, f16_t* out,
                                 const double* src, int from_out, double scale, unsigned* err, bool vtiles,
                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense);
+// The last launch of a sum fused with the optimiser update (skml_sparse_decode_sum_step_*): the
+// same default forms, but a finished tile's doubles, x scale, go from LDS into the update of w / m / v
+// (float, or double when `wide`; 16-byte aligned, m and v null for SGD) and are never stored.
+// launch_agg_tiles_live: the same launch with toAuto's count of |sum x scale| > 1e-8 in place of
+// the update (*count zeroed by the caller on `st`); it touches no state.
+hipError_t launch_agg_tiles_step(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense, const OptConsts& k, int wide,
+                                 void* w, void* m, void* v);
+hipError_t launch_agg_tiles_live(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense, unsigned long long* count);
+// What a tile launch would report in err bits 1 and 2 (a key outside its tile, a key repeated across
+// a payload's groups), from the keys alone: run before a fused launch, which must not start on
+// payloads it would refuse.
+hipError_t launch_agg_check(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, unsigned* err,
+                            bool vtiles, const int32_t* kbase);
 
 // Exported sparse payload: one contiguous device blob (skml_sparse_export / _import, the unit the
 // RCCL all-gather moves).  Offsets are from the blob start, every section 256-byte aligned.

@@ -1,6 +1,8 @@
 // skml_sparse.hip -- CDNA4 (gfx950) kernels of the sparse codec: Gradient.sum and Sort.merge over
 // restored payloads.
 //   k_agg_*          Gradient.sum of restored payloads, tiled over the dense sum.
+//   k_agg_*_sink     the sum's last launch with the optimiser update (or toAuto's count) where the store is;
+//   k_agg_check*     the keys-only check that runs before it (skml_sparse_decode_sum_step_*).
 //   k_merge_round    Sort.merge (util/Sort.java:362-379) as rounds of stable merge-path merges.
 //   k_rs_*           Sort.merge in one pass over key ranges (the regular case).
 // The other stages have files of their own: skml_sparse_compact / _partition / _minmax / _delta /
@@ -11,6 +13,7 @@
 #include <type_traits>
 
 #include "skml_device.hpp"
+#include "skml_opt.hpp"
 #include "skml_sparse.h"
 #include "skml_sparse_device.hpp"
 
@@ -189,6 +192,67 @@ __device__ __forceinline__ void agg_store_vec(O* out, int64_t x, const double (&
     }
 }
 
+// Sinks of a sum's last tile launch that store no sum (skml_sparse_decode_sum_step_*).  They stand
+// in the position of O, `out` pointing at the kernel's own copy: a finished tile's doubles, x scale,
+// go from LDS straight into the optimiser update of w / m / v (OptSink), or into toAuto's count of
+// |g| > 1e-8 (CountSink, SKML_OPT_AUTO's extra launch), and never reach memory.
+template <bool ADAM, typename W>
+struct OptSink {
+    W *w, *m, *v;  // dim values each, 16-byte aligned; m, v unused for SGD
+    OptConsts k;
+};
+struct CountSink {
+    unsigned long long* count;  // zeroed by the caller on the launch's stream
+};
+template <typename O>
+struct is_opt_sink : std::false_type {};
+template <bool ADAM, typename W>
+struct is_opt_sink<OptSink<ADAM, W>> : std::true_type {};
+template <typename O>
+constexpr bool agg_is_sink = is_opt_sink<O>::value || std::is_same<O, CountSink>::value;
+
+// A finished tile of TILE doubles in LDS into the update, by the THREADS lanes that built it (this
+// one: l).  A whole tile goes in rounds of one 16-byte access per state array and lane (2 doubles or
+// 4 floats: 1 KB contiguous per wave and instruction, and only one round's state in registers); tile
+// starts are multiples of 512, so whole tiles are aligned whenever the arrays are.  The ragged last
+// tile goes element by element.  Every element has one owner: the update is in place.  LIVE: a
+// round whose elements are all dead is not stored.
+template <int TILE, int THREADS, bool ADAM, typename W>
+__device__ __forceinline__ void sink_tile(const OptSink<ADAM, W>& s, const double* t, int l, int64_t k0, int64_t nk,
+                                          double scale) {
+    constexpr int N = 16 / (int)sizeof(W);
+    static_assert(TILE % (THREADS * N) == 0, "whole rounds of 16-byte accesses");
+    if (nk == TILE) {
+#pragma unroll
+        for (int q = 0; q < TILE / (THREADS * N); q++) {
+            const int x = THREADS * N * q + N * l;
+            double g[N];
+            bool any = !s.k.live;
+#pragma unroll
+            for (int i = 0; i < N; i++) {
+                g[i] = scale != 1.0 ? __dmul_rn(t[x + i], scale) : t[x + i];
+                any |= fabs(g[i]) > 1e-8;
+            }
+            StateN<ADAM, W, N> st;
+            st.load(s.w, s.m, s.v, k0 + x);
+            st.apply(g, s.k);
+            if (any) st.store(s.w, s.m, s.v, k0 + x);
+        }
+    } else {
+        for (int x = l; x < nk; x += THREADS)
+            opt_apply_at<ADAM>(scale != 1.0 ? __dmul_rn(t[x], scale) : t[x], s.w, s.m, s.v, k0 + x, s.k);
+    }
+}
+// The same tile into the live count: every lane reaches every ballot.
+template <int TILE, int THREADS>
+__device__ __forceinline__ void count_tile(LiveCount& lc, const double* t, int l, int64_t nk, double scale) {
+#pragma unroll
+    for (int q = 0; q < TILE / THREADS; q++) {
+        const int x = THREADS * q + l;
+        lc.add(x < nk && fabs(scale != 1.0 ? __dmul_rn(t[x], scale) : t[x]) > 1e-8);
+    }
+}
+
 template <typename O>
 __device__ __forceinline__ void agg_tiles_w_body(const AggPayload* __restrict__ pays, int P, int64_t ntiles,
                                                  int64_t dim, O* out, const double* src, int from_out, double scale,
@@ -230,8 +294,15 @@ __device__ __forceinline__ void agg_tiles_w_body(const AggPayload* __restrict__ 
     // The store of tile t - 1 is deferred until tile t's element loads are in flight, and the
     // zeroing of the LDS sum follows it, so both overlap those loads' latency.
     int64_t prev_k0 = -1, prev_nk = 0;
+    [[maybe_unused]] LiveCount lc;
     auto store_prev = [&]() {
-        if constexpr (std::is_same<O, double>::value) {
+        if constexpr (agg_is_sink<O>) {  // the update, or the count, where the store is
+            if (prev_k0 < 0) return;
+            if constexpr (is_opt_sink<O>::value)
+                sink_tile<kAggTile, kAggThreads>(*out, acc, (int)threadIdx.x, prev_k0, prev_nk, scale);
+            else
+                count_tile<kAggTile, kAggThreads>(lc, acc, (int)threadIdx.x, prev_nk, scale);
+        } else if constexpr (std::is_same<O, double>::value) {
             if (prev_k0 >= 0)
                 for (int x = threadIdx.x; x < prev_nk; x += kAggThreads)
                     out[prev_k0 + x] = scale == 1.0 ? acc[x] : __dmul_rn(acc[x], scale);
@@ -371,6 +442,10 @@ __device__ __forceinline__ void agg_tiles_w_body(const AggPayload* __restrict__ 
     __syncthreads();
     store_prev();
     if (bad) atomicOr(err, bad);
+    if constexpr (std::is_same<O, CountSink>::value) {
+        __shared__ unsigned long long s_cnt;
+        lc.finish(&s_cnt, out->count);
+    }
 }
 __global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w(const AggPayload* __restrict__ pays, int P,
                                                             int64_t ntiles, int64_t dim, double* __restrict__ out,
@@ -384,6 +459,14 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w_o(const AggPayload*
                                                               const double* __restrict__ src, int from_out,
                                                               double scale, unsigned* __restrict__ err) {
     agg_tiles_w_body<O>(pays, P, ntiles, dim, out, src, from_out, scale, err);
+}
+// the same sum into a sink (OptSink / CountSink), passed by value
+template <typename S>
+__global__ __launch_bounds__(kAggThreads) void k_agg_tiles_w_sink(const AggPayload* __restrict__ pays, int P,
+                                                                 int64_t ntiles, int64_t dim, S sink,
+                                                                 const double* __restrict__ src, int from_out,
+                                                                 double scale, unsigned* __restrict__ err) {
+    agg_tiles_w_body<S>(pays, P, ntiles, dim, &sink, src, from_out, scale, err);
 }
 
 // One wave per tile of kAggVTile keys, staged: lane 8p + g of the wave holds the run piece of
@@ -878,11 +961,16 @@ __device__ __forceinline__ void agg_rmw_body(
         }
     };
     int64_t prev_k0 = -1, prev_nk = 0;
+    [[maybe_unused]] LiveCount lc;
     auto store_prev = [&](int l) {  // the previous tile's sums, x scale, 1 KB per store instruction
         if (prev_k0 < 0) return;
-        O* o = out + prev_k0;
-        const bool whole = prev_nk == kTile && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
-        if constexpr (!std::is_same<O, double>::value) {  // kV values per lane and store instruction
+        [[maybe_unused]] O* o = out + prev_k0;
+        [[maybe_unused]] const bool whole = prev_nk == kTile && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+        if constexpr (is_opt_sink<O>::value) {  // the update, or the count, where the store is
+            sink_tile<kTile, 64>(*out, T, l, prev_k0, prev_nk, scale);
+        } else if constexpr (std::is_same<O, CountSink>::value) {
+            count_tile<kTile, 64>(lc, T, l, prev_nk, scale);
+        } else if constexpr (!std::is_same<O, double>::value) {  // kV values per lane and store instruction
             constexpr int kV = agg_out_vec<O>();
             static_assert(kTile % (64 * kV) == 0, "whole rows of 16-byte stores: a smaller tile would store nothing");
 #pragma unroll
@@ -1041,6 +1129,10 @@ __device__ __forceinline__ void agg_rmw_body(
     }
     store_prev(lane);
     if (bad) atomicOr(err, bad);
+    if constexpr (std::is_same<O, CountSink>::value) {
+        __shared__ unsigned long long s_cnt;
+        lc.finish(&s_cnt, out->count);
+    }
 }
 template <int BITS, int WAVES, int PER, bool DENSE>
 __global__ __launch_bounds__(64 * WAVES) void k_agg_rmw(
@@ -1054,6 +1146,181 @@ __global__ __launch_bounds__(64 * WAVES) void k_agg_rmw_o(
     const double* __restrict__ src, int from_out, double scale, unsigned* __restrict__ err,
     const int32_t* __restrict__ kbase, const uint8_t* __restrict__ bbase) {
     agg_rmw_body<BITS, WAVES, PER, DENSE, O>(pays, P, ntiles, dim, out, src, from_out, scale, err, kbase, bbase);
+}
+template <int BITS, int WAVES, int PER, bool DENSE, typename S>
+__global__ __launch_bounds__(64 * WAVES) void k_agg_rmw_sink(
+    const AggPayload* __restrict__ pays, int P, int64_t ntiles, int64_t dim, S sink, const double* __restrict__ src,
+    int from_out, double scale, unsigned* __restrict__ err, const int32_t* __restrict__ kbase,
+    const uint8_t* __restrict__ bbase) {
+    agg_rmw_body<BITS, WAVES, PER, DENSE, S>(pays, P, ntiles, dim, &sink, src, from_out, scale, err, kbase, bbase);
+}
+
+// ---- the keys-only check before a fused last launch (skml_sparse_decode_sum_step_*) ----
+// The tile kernels find a key outside its tile (err bit 1) and a key repeated across a payload's
+// groups (err bit 2) in the pass that builds the sums, which for a fused launch is the pass that
+// changes w / m / v: too late to refuse.  k_agg_check finds both first, from the keys alone.  It is
+// k_agg_rmw's walk -- one wave per 2^BITS-key tile, persistent, tile_walk_xcd, lane 8p + g holding
+// the run piece of payload p, group g, the pieces concatenated and each lane taking elements j = l +
+// 64 u, the next tile's bounds and keys loaded before this tile is marked -- without the bins, the
+// quantValues and the sum tile.  Since nothing is added, payload order does not matter: all of a
+// tile's keys are marked at once in one 64-word bitmap of the wave, key x of payload p at word x %
+// 64, bit 8 p + x / 64 (one LDS atomic OR that returns the old word per key; a row's random keys
+// spread over the 64 words).  A bit already set is err bit 2, a key outside the tile err bit 1:
+// the bits, and so the messages, the sum kernels would have given.
+template <int BITS, int WAVES, int PER>
+__global__ __launch_bounds__(64 * WAVES) void k_agg_check(const AggPayload* __restrict__ pays, int P, int64_t ntiles,
+                                                          int64_t dim, unsigned* __restrict__ err,
+                                                          const int32_t* __restrict__ kbase) {
+    constexpr int kTile = 1 << BITS;
+    static_assert(kTile / 64 == 8 && kAggPB == 8, "eight bits per payload, eight payloads per 64-bit word");
+    __shared__ unsigned long long here[WAVES][64];
+    __shared__ int32_t pre[2][WAVES][65];
+    __shared__ int32_t pk[2][WAVES][64];  // piece s's key element base minus its first index pre[s]
+    __shared__ uint8_t pcs[WAVES][64 * PER];  // piece of element j
+    __shared__ AggPayload pl[kAggPB];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (threadIdx.x < P * (int)(sizeof(AggPayload) / 8))
+        reinterpret_cast<uint64_t*>(pl)[threadIdx.x] = reinterpret_cast<const uint64_t*>(pays)[threadIdx.x];
+    __syncthreads();
+    const int pl_l = lane >> 3, g_l = lane & 7;
+    const bool lane_on = pl_l < P && g_l < pl[pl_l].G;
+    const int32_t* bd = lane_on ? pl[pl_l].bounds + (int64_t)g_l * (ntiles + 1) : nullptr;
+    const int32_t gk_off = lane_on ? pl[pl_l].gk_off : 0;
+    unsigned long long* H = here[wave];
+    unsigned bad = 0;
+    int32_t nb0 = 0, nb1 = 0;
+    auto fetch = [&](int64_t tt) {
+        if (lane_on && tt < ntiles) {
+            nb0 = gload<int32_t>(bd, tt);
+            nb1 = gload<int32_t>(bd, tt + 1);
+        }
+    };
+    auto plan = [&](int buf, int32_t b0, int32_t b1) -> int {
+        const int32_t len = lane_on && b1 > b0 ? b1 - b0 : 0;
+        const int32_t x = (int32_t)wave_incl_scan_u32((uint32_t)len);
+        pre[buf][wave][lane + 1] = x;
+        if (lane == 0) pre[buf][wave][0] = 0;
+        pk[buf][wave][lane] = gk_off + b0 - (x - len);
+        __builtin_amdgcn_wave_barrier();
+        return __builtin_amdgcn_readlane(x, 63);
+    };
+    // keys of elements j = lane + 64 u < min(total, 64 PER), with their payloads in pp
+    auto load = [&](int buf, int total, int32_t (&kk)[PER], uint32_t& pp) {
+        const int e0 = pre[buf][wave][lane], e1 = min(pre[buf][wave][lane + 1], 64 * PER);
+        for (int e = e0; e < e1; e++) pcs[wave][e] = (uint8_t)lane;
+        __builtin_amdgcn_wave_barrier();
+        pp = 0;
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            const int j = lane + 64 * u;
+            kk[u] = INT32_MIN;
+            if (j < total) {
+                const int sp = (int)pcs[wave][j];
+                kk[u] = gload<int32_t>(kbase, (uint32_t)(pk[buf][wave][sp] + j));
+                pp |= (uint32_t)(sp >> 3) << (4 * u);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();  // pcs is the next load's too
+    };
+    static_assert(PER <= 8, "a payload number per element in 4 bits of pp");
+    const TileWalk tw = tile_walk_xcd(blockIdx.x, gridDim.x, wave, WAVES, ntiles);
+    int buf = 0, total = 0;
+    int32_t kk[PER], kn[PER];
+    uint32_t pp = 0, pn = 0;
+    if (tw.t0 < tw.t1) {
+        fetch(tw.t0);
+        total = plan(0, nb0, nb1);
+        load(0, total, kk, pp);
+        fetch(tw.t0 + tw.step);
+    }
+    for (int64_t t = tw.t0; t < tw.t1; t += tw.step) {
+        const int64_t k0 = t << BITS, nk = std::min<int64_t>(kTile, dim - k0);
+        int total_n = 0;
+        if (t + tw.step < tw.t1) {
+            total_n = plan(buf ^ 1, nb0, nb1);
+            load(buf ^ 1, total_n, kn, pn);
+            fetch(t + 2 * tw.step);
+        }
+        H[lane] = 0ull;
+        __builtin_amdgcn_wave_barrier();
+        const int32_t k0i = (int32_t)k0;  // dim <= 2^31: tile starts fit int32
+        auto mark = [&](int32_t k, int p) {
+            const uint32_t xk = (uint32_t)k - (uint32_t)k0i;
+            if (xk >= (uint32_t)nk) {
+                bad |= 1u;
+            } else {
+                const unsigned long long bit = 1ull << (8 * p + (int)(xk >> 6));
+                if (atomicOr(&H[xk & 63], bit) & bit) bad |= 2u;
+            }
+        };
+#pragma unroll
+        for (int u = 0; u < PER; u++)
+            if (lane + 64 * u < total) mark(kk[u], (int)((pp >> (4 * u)) & 15u));
+        for (int j = 64 * PER + lane; j < total; j += 64) {  // rows past the registers
+            int sp = 0;
+#pragma unroll
+            for (int step = 32; step >= 1; step >>= 1)
+                if (pre[buf][wave][sp + step] <= j) sp += step;
+            mark(gload<int32_t>(kbase, (uint32_t)(pk[buf][wave][sp] + j)), sp >> 3);
+        }
+        __builtin_amdgcn_wave_barrier();
+        buf ^= 1;
+        total = total_n;
+        pp = pn;
+#pragma unroll
+        for (int u = 0; u < PER; u++) kk[u] = kn[u];
+    }
+    if (bad) atomicOr(err, bad);
+}
+// The check for the payloads the 512-key form cannot take (more than 8 groups or 256 quantValues;
+// any P): one wave per tile of kAggTile keys, the batch's payloads one after the other as
+// k_agg_tiles_w's waves walk them -- lane g holds group g's run piece, the pieces are concatenated
+// and the lanes take elements j = l + 64 u -- each payload marked in the wave's 4,096-bit map (key
+// x at word x % 128, bit x / 128), cleared between payloads.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_agg_check_w(const AggPayload* __restrict__ pays, int P, int64_t ntiles,
+                                                            int64_t dim, unsigned* __restrict__ err) {
+    __shared__ uint32_t here[WAVES][kAggTile / 32];
+    __shared__ int32_t pre[WAVES][kMaxGroups + 1];  // run prefix (elements) per group, this tile
+    __shared__ int32_t rs[WAVES][kMaxGroups];       // run start (element index in the payload)
+    static_assert(kAggTile / 32 == 128 && kMaxGroups == 64, "two bitmap words and one group per lane");
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    unsigned bad = 0;
+    const TileWalk tw = tile_walk_xcd(blockIdx.x, gridDim.x, wave, WAVES, ntiles);
+    for (int64_t t = tw.t0; t < tw.t1; t += tw.step) {
+        const int64_t k0 = t * kAggTile, nk = std::min<int64_t>(kAggTile, dim - k0);
+        const int32_t k0i = (int32_t)k0;
+        for (int p = 0; p < P; p++) {
+            const AggPayload a = pays[p];
+            int32_t b0 = 0, len = 0;
+            if (lane < a.G) {
+                const int32_t* bd = a.bounds + (int64_t)lane * (ntiles + 1);
+                b0 = gload<int32_t>(bd, t);
+                const int32_t b1 = gload<int32_t>(bd, t + 1);
+                len = b1 > b0 ? b1 - b0 : 0;
+            }
+            const int32_t x = (int32_t)wave_incl_scan_u32((uint32_t)len);
+            pre[wave][lane + 1] = x;
+            if (lane == 0) pre[wave][0] = 0;
+            rs[wave][lane] = b0;
+            here[wave][lane] = here[wave][lane + 64] = 0u;
+            __builtin_amdgcn_wave_barrier();
+            const int total = __builtin_amdgcn_readlane(x, 63);
+            for (int j = lane; j < total; j += 64) {
+                const int g = agg_search32(pre[wave], kMaxGroups + 1, j);
+                const uint32_t xk =
+                    (uint32_t)gload<int32_t>(a.gk, (int64_t)rs[wave][g] + (j - pre[wave][g])) - (uint32_t)k0i;
+                if (xk >= (uint32_t)nk) {
+                    bad |= 1u;
+                } else {
+                    const uint32_t bit = 1u << (xk >> 7);
+                    if (atomicOr(&here[wave][xk & 127], bit) & bit) bad |= 2u;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (bad) atomicOr(err, bad);
 }
 
 // The staged wave-tile form is the default for payloads of at most 8 groups and 256 quantValues
@@ -1167,6 +1434,82 @@ hipError_t launch_agg_tiles_f16(hipStream_t st, const AggPayload* pays, int P, i
                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
     return launch_agg_tiles_o<f16_t>(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vtiles, kbase, bbase,
                                      any_dense);
+}
+
+// The last launch of a sum into a sink: launch_agg_tiles_o's forms and grids.
+template <typename S>
+hipError_t launch_agg_tiles_sink(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 const S& sink, const double* src, int from_out, double scale, unsigned* err,
+                                 bool vtiles, const int32_t* kbase, const uint8_t* bbase, bool any_dense) {
+    if (ntiles <= 0) return hipSuccess;
+    if (from_out && !src) return hipErrorInvalidValue;
+    if (vtiles) {
+        if (P < 1 || P > kAggVPayloads) return hipErrorInvalidValue;
+#define SKML_RMW_LAUNCH(DENSE)                                                                                      \
+    do {                                                                                                            \
+        static const int res = resident_blocks(k_agg_rmw_sink<kAggVBits, 8, 8, DENSE, S>, kAggThreads);              \
+        const int64_t all = sp_tiles(ntiles, 8);                                                                    \
+        const unsigned grid = (unsigned)(res <= 0 ? all : std::min<int64_t>(all, res));                             \
+        hipLaunchKernelGGL((k_agg_rmw_sink<kAggVBits, 8, 8, DENSE, S>), dim3(grid), dim3(kAggThreads), 0, st, pays, \
+                           P, ntiles, dim, sink, src, from_out, scale, err, kbase, bbase);                          \
+    } while (0)
+        if (any_dense) SKML_RMW_LAUNCH(true);
+        else SKML_RMW_LAUNCH(false);
+#undef SKML_RMW_LAUNCH
+        return hipGetLastError();
+    }
+    static const int resident = resident_blocks(k_agg_tiles_w_sink<S>, kAggThreads);
+    const unsigned grid = (unsigned)(resident <= 0 ? ntiles : std::min<int64_t>(ntiles, resident));
+    hipLaunchKernelGGL(k_agg_tiles_w_sink<S>, dim3(grid), dim3(kAggThreads), 0, st, pays, P, ntiles, dim, sink, src,
+                       from_out, scale, err);
+    return hipGetLastError();
+}
+template <typename W>
+static hipError_t launch_agg_step_w(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                    const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                    const int32_t* kbase, const uint8_t* bbase, bool any_dense, const OptConsts& k,
+                                    void* w, void* m, void* v) {
+    if (k.adam)
+        return launch_agg_tiles_sink(st, pays, P, ntiles, dim,
+                                     OptSink<true, W>{static_cast<W*>(w), static_cast<W*>(m), static_cast<W*>(v), k}, src,
+                                     from_out, scale, err, vtiles, kbase, bbase, any_dense);
+    return launch_agg_tiles_sink(st, pays, P, ntiles, dim, OptSink<false, W>{static_cast<W*>(w), nullptr, nullptr, k}, src,
+                                 from_out, scale, err, vtiles, kbase, bbase, any_dense);
+}
+hipError_t launch_agg_tiles_step(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense, const OptConsts& k, int wide,
+                                 void* w, void* m, void* v) {
+    if (wide)
+        return launch_agg_step_w<double>(st, pays, P, ntiles, dim, src, from_out, scale, err, vtiles, kbase, bbase,
+                                         any_dense, k, w, m, v);
+    return launch_agg_step_w<float>(st, pays, P, ntiles, dim, src, from_out, scale, err, vtiles, kbase, bbase, any_dense,
+                                    k, w, m, v);
+}
+hipError_t launch_agg_tiles_live(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim,
+                                 const double* src, int from_out, double scale, unsigned* err, bool vtiles,
+                                 const int32_t* kbase, const uint8_t* bbase, bool any_dense, unsigned long long* count) {
+    return launch_agg_tiles_sink(st, pays, P, ntiles, dim, CountSink{count}, src, from_out, scale, err, vtiles, kbase,
+                                 bbase, any_dense);
+}
+
+hipError_t launch_agg_check(hipStream_t st, const AggPayload* pays, int P, int64_t ntiles, int64_t dim, unsigned* err,
+                            bool vtiles, const int32_t* kbase) {
+    if (ntiles <= 0) return hipSuccess;
+    constexpr int kWaves = kAggThreads / 64;
+    const int64_t all = sp_tiles(ntiles, kWaves);  // persistent: as many workgroups as are resident at once
+    if (vtiles) {
+        if (P < 1 || P > kAggVPayloads) return hipErrorInvalidValue;  // one lane per (payload, group)
+        static const int res = resident_blocks(k_agg_check<kAggVBits, kWaves, 8>, kAggThreads);
+        const unsigned grid = (unsigned)(res <= 0 ? all : std::min<int64_t>(all, res));
+        hipLaunchKernelGGL((k_agg_check<kAggVBits, kWaves, 8>), dim3(grid), dim3(kAggThreads), 0, st, pays, P, ntiles,
+                           dim, err, kbase);
+        return hipGetLastError();
+    }
+    static const int res = resident_blocks(k_agg_check_w<kWaves>, kAggThreads);
+    const unsigned grid = (unsigned)(res <= 0 ? all : std::min<int64_t>(all, res));
+    hipLaunchKernelGGL(k_agg_check_w<kWaves>, dim3(grid), dim3(kAggThreads), 0, st, pays, P, ntiles, dim, err);
+    return hipGetLastError();
 }
 
 // live entries (|quantValues[bin]| > 1e-8) of a restored payload, for toAuto's dense / sparse choice

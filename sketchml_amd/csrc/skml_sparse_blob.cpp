@@ -327,6 +327,29 @@ inline hipError_t launch_agg_last(hipStream_t st, const AggPayload* pays, int P,
     return launch_agg_tiles_f16(st, pays, P, ntiles, dim, out, src, from_out, scale, err, vt, kb, bb, any_dense);
 }
 
+// O of skml_sparse_decode_sum_step_*: no sum is returned.  The launches before the last keep the sum
+// in the accumulator, as for a narrow O; before the last one a keys-only check (launch_agg_check)
+// finds what that launch would refuse and err is read, so that the fused launch
+// (launch_agg_tiles_step), the only one that touches w / m / v, runs on payloads known to be good.
+struct StepSink {
+    const skml_opt_params* p;
+    int wide;  // w / m / v hold doubles (else floats)
+    void *w, *m, *v;
+};
+
+// err, read back once on the context's stream (synchronises), as Gradient.sum's refusal
+int sum_refusal(skml_ctx* c, const unsigned* err, int64_t dim) {
+    unsigned bad = 0;
+    if (int e = sync_to_host(c, &bad, err, sizeof(bad))) return e;
+    if (bad & 1u)
+        return fail(SKML_E_ARG, "a payload holds a key outside [0, %lld), a non-ascending run or a bin outside its "
+                                "values (SparseDoubleGradient requires ascending indices in range)", (long long)dim);
+    if (bad & 2u)
+        return fail(SKML_E_ARG, "requirement failed: Indices are not strictly increasing (a key repeated across a "
+                                "payload's groups; SparseDoubleGradient.scala:12)");
+    return SKML_OK;
+}
+
 template <typename O>
 int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale, O* out) {
     if (!c || !blobs || P < 1 || dim < 0 || dim > (int64_t)INT32_MAX || (dim > 0 && !out) || stride % 256)
@@ -473,13 +496,39 @@ int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int
             for (size_t q = c0; q < c0 + nc; q++) any_dense |= pays[q].dense_form != 0;
             const int from_out = first && c0 == 0 ? 0 : 1;
             const bool final_launch = last && c0 + nc == pays.size();
+            [[maybe_unused]] int live = 0;
+            if constexpr (std::is_same<O, StepSink>::value) {
+                if (final_launch) {
+                    // check first, then update: the keys-only check of this launch's payloads, then the one
+                    // read of err, which covers every earlier batch's restore and tiles, this batch's
+                    // restore and the check; a refusal leaves w / m / v as they were
+                    {
+                        KernelTimer kt(c, SKML_K_SPARSE_CHECK);
+                        HIP_TRY(launch_agg_check(st, d_pays + c0, (int)nc, ntiles, dim, err, vt, gk));
+                    }
+                    if (int e = sum_refusal(c, err, dim)) return e;
+                    live = out->p->select == SKML_OPT_LIVE;
+                    if (out->p->select == SKML_OPT_AUTO) {  // the same launch with the count in place of the update
+                        unsigned long long* cnt = nullptr;
+                        if (int e = opt_counter_zeroed(c, &cnt)) return e;
+                        HIP_TRY(launch_agg_tiles_live(st, d_pays + c0, (int)nc, ntiles, dim, accd, from_out, scale, err, vt,
+                                                      gk, gbn, any_dense, cnt));
+                        if (int e = opt_auto_choice(c, cnt, dim, &live)) return e;
+                    }
+                }
+            }
             t_sum_launches++;
             if constexpr (std::is_same<O, double>::value) {
                 HIP_TRY(launch_agg_tiles(st, d_pays + c0, (int)nc, ntiles, dim, out, from_out,
                                          final_launch ? scale : 1.0, err, vt, gk, gbn, any_dense));
             } else if (final_launch) {
-                HIP_TRY(launch_agg_last(st, d_pays + c0, (int)nc, ntiles, dim, out, accd, from_out, scale, err, vt, gk,
-                                        gbn, any_dense));
+                if constexpr (std::is_same<O, StepSink>::value)
+                    HIP_TRY(launch_agg_tiles_step(st, d_pays + c0, (int)nc, ntiles, dim, accd, from_out, scale, err, vt, gk,
+                                                  gbn, any_dense, opt_consts_of(*out->p, live), out->wide, out->w, out->m,
+                                                  out->v));
+                else
+                    HIP_TRY(launch_agg_last(st, d_pays + c0, (int)nc, ntiles, dim, out, accd, from_out, scale, err, vt, gk,
+                                            gbn, any_dense));
             } else {
                 if (!accd && !(accd = scratch<double>(c, kSlotAggAcc, (size_t)dim)))
                     return fail(SKML_E_OOM, "decode_sum accumulator (%lld doubles)", (long long)dim);
@@ -491,15 +540,25 @@ int decode_sum_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int
         first = false;
         at = end;
     }
-    unsigned bad = 0;
-    if (int e = sync_to_host(c, &bad, err, sizeof(bad))) return e;
-    if (bad & 1u)
-        return fail(SKML_E_ARG, "a payload holds a key outside [0, %lld), a non-ascending run or a bin outside its "
-                                "values (SparseDoubleGradient requires ascending indices in range)", (long long)dim);
-    if (bad & 2u)
-        return fail(SKML_E_ARG, "requirement failed: Indices are not strictly increasing (a key repeated across a "
-                                "payload's groups; SparseDoubleGradient.scala:12)");
-    return SKML_OK;
+    if constexpr (std::is_same<O, StepSink>::value) {
+        // the check passed before the fused launch; that launch keeps its own account of the same errors
+        unsigned bad = 0;
+        if (int e = sync_to_host(c, &bad, err, sizeof(bad))) return e;
+        if (bad) return fail(SKML_E_HIP, "internal: check and sum disagree (err %u after a clean check)", bad);
+        return SKML_OK;
+    } else {
+        return sum_refusal(c, err, dim);
+    }
+}
+
+// skml_sparse_decode_sum_step_*: the sum's arguments and refusals, the dense step's parameters and state.
+int decode_sum_step_any(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                        const skml_opt_params* p, int wide, void* w, void* m, void* v) {
+    const size_t sb = dim > 0 ? (size_t)dim * (wide ? 8 : 4) : 0;
+    Range r[4] = {{w, sb, "w"}, {m, sb, "m"}, {v, sb, "v"}, {blobs, P > 0 ? (size_t)P * stride : 0, "blobs"}};
+    if (const int st = opt_check_common(c, p, r, 4)) return st;
+    StepSink sink{p, wide, w, m, v};
+    return decode_sum_any<StepSink>(c, blobs, P, stride, dim, scale, &sink);
 }
 
 }  // namespace
@@ -524,6 +583,16 @@ int skml_sparse_decode_sum_bf16(skml_ctx* c, const void* blobs, int32_t P, size_
 int skml_sparse_decode_sum_f16(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
                                uint16_t* out) {
     return decode_sum_any<f16_t>(c, blobs, P, stride, dim, scale, reinterpret_cast<f16_t*>(out));
+}
+
+int skml_sparse_decode_sum_step_f32(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                                    const skml_opt_params* p, float* w, float* m, float* v) {
+    return decode_sum_step_any(c, blobs, P, stride, dim, scale, p, 0, w, m, v);
+}
+
+int skml_sparse_decode_sum_step_f64(skml_ctx* c, const void* blobs, int32_t P, size_t stride, int64_t dim, double scale,
+                                    const skml_opt_params* p, double* w, double* m, double* v) {
+    return decode_sum_step_any(c, blobs, P, stride, dim, scale, p, 1, w, m, v);
 }
 
 }  // extern "C"

@@ -193,6 +193,19 @@ def decode_sum_update_fixed_point(ctx_handle, payloads: torch.Tensor, nranks: in
     optimizer.step_fixed_payloads(ctx_handle, payloads, nranks, stride, scale, weight, select)
 
 
+def decode_sum_update_sparse(ctx_handle, blobs: torch.Tensor, nranks: int, stride: int, dim: int, scale: float,
+                             optimizer, weight: torch.Tensor, select: int = _lib.SKML_OPT_ALL) -> None:
+    """decode_sum_update for gathered sparse blobs (exchange_sparse's all-gather output;
+    skml_sparse_decode_sum_step_f32 / _f64): Gradient.sum of the SketchGradients in double, scaled,
+    goes into the update where the sum's last tile launch would have stored it.  Blobs the sum
+    refuses (a key repeated across a payload's groups, an empty payload) are refused before anything
+    is updated."""
+    if int(dim) != optimizer.dim:
+        raise SketchMLException(f"decode_sum_update_sparse: dim={dim}, the optimiser's dim is {optimizer.dim}")
+    optimizer._begin_update()
+    optimizer.step_sparse_payloads(ctx_handle, blobs, nranks, stride, scale, weight, select)
+
+
 # ---- one split table across ranks (SURVEY §8e single-split-table mode) ----------------------
 def parallel_slices(n_total: int, parts: int) -> list[int]:
     """Slice sizes of QuantileQuantizer.parallelQuantize (QuantileQuantizer.java:66-68): n/T

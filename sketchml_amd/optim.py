@@ -1,6 +1,7 @@
 """The optimiser update on the device: the reference's GradientDescent and Adam
 (ml/objective/GradientDescent.scala:16-21,89-117, ml/objective/Adam.scala:16-77) over the
-skml_opt_step_* / skml_dense_decode_sum_step_* / skml_fixed_decode_sum_step_* entries of include/skml.h.
+skml_opt_step_* / skml_dense_decode_sum_step_* / skml_fixed_decode_sum_step_* /
+skml_sparse_decode_sum_step_* entries of include/skml.h.
 
 The weight is a device tensor (float64 as the reference's DenseVector, or float32); Adam's m and
 v are tensors of the weight's dtype that the optimiser owns.  All arithmetic runs in double in the
@@ -213,6 +214,19 @@ class GradientDescent:
               else _lib.lib.skml_fixed_decode_sum_step_f32)
         check(fn(ctx_handle, _ptr(payloads), int(nranks), int(stride), self.dim, float(scale), C.byref(p),
                  _ptr(weight), _ptr(m), _ptr(v)), "fixed_decode_sum_step")
+
+    def step_sparse_payloads(self, ctx_handle, blobs: torch.Tensor, nranks: int, stride: int, scale: float,
+                             weight: torch.Tensor, select: int = ALL) -> None:
+        """skml_sparse_decode_sum_step_*: the same for gathered sparse blobs (SketchGradient payloads,
+        sparse.exchange_sparse's all-gather output).  The payloads are checked before the one launch
+        that updates: a refused call leaves the weight, m and v as they were."""
+        self._check_weight(weight)
+        m, v = self._state(weight)
+        p = self.params(select)
+        fn = (_lib.lib.skml_sparse_decode_sum_step_f64 if weight.dtype == torch.float64
+              else _lib.lib.skml_sparse_decode_sum_step_f32)
+        check(fn(ctx_handle, _ptr(blobs), int(nranks), int(stride), self.dim, float(scale), C.byref(p),
+                 _ptr(weight), _ptr(m), _ptr(v)), "sparse_decode_sum_step")
 
 
 class Adam(GradientDescent):

@@ -571,6 +571,35 @@ int skml_glm_gradient_dense_f32(skml_ctx* ctx, const skml_glm_dense_data* data, 
 #define SKML_GLM_DENSE_ROW_GROUP_AT 4 /* 64-row waves from which two share a workgroup */
 #define SKML_GLM_DENSE_COL_GROUP_AT 5 /* column waves from which four share a workgroup */
 int skml_debug_glm_dense_constant(int which);
+/* Dense instances whose x is stored as fp32, bf16 or fp16 (x_kind: SKML_X_*; 16-bit values travel as
+ * uint16_t).  pitch: the elements between the starts of two rows, pitch >= dim; x is 16-byte aligned and
+ * pitch * sizeof(X) a multiple of 16, so every row starts on a 16-byte boundary whatever dim is.  The
+ * pitch - dim pad elements of a row are readable memory of any content: the kernels may load them, and
+ * none reaches a sum (a pad full of NaN changes no output bit).  label[rows] stays double. */
+#define SKML_X_F32 0
+#define SKML_X_BF16 1
+#define SKML_X_F16 2
+typedef struct skml_glm_dense_lowp_data {
+    int64_t rows, dim, pitch;
+    const void* x;
+    const double* label;
+    int32_t x_kind;
+} skml_glm_dense_lowp_data;
+/* skml_glm_gradient_dense_* over such an x (the suffix is the weight's type, as there): every output has
+ * the bits skml_glm_gradient_dense_* gives on the same array widened element by element to double, which
+ * is exact for every bit pattern (subnormals, +-0, Inf and NaN included).  Outputs, NULL rules, the single
+ * synchronisation, stream behaviour and timing ids are the dense twin's.  SKML_E_ARG, with nothing
+ * written: as skml_glm_gradient_dense_*, an unknown x_kind, pitch < dim, a pitch or an x that breaks the
+ * 16-byte rule, and rows * pitch * sizeof(X) beyond an int64.  skml_glm_finish_* serves the gradient. */
+int skml_glm_gradient_dense_lowp_f64(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                     int32_t loss_kind, const double* w_dev, double* pre_out, double* coef_out,
+                                     double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_lowp_f32(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                     int32_t loss_kind, const float* w_dev, double* pre_out, double* coef_out,
+                                     double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+/* The shape constants of these kernels (csrc/skml_glm_dense_lowp.hpp) for an x of kind x_kind, `which` as
+ * SKML_GLM_DENSE_* above (STRIDE in dwords); -1 for any other x_kind or `which`. */
+int skml_debug_glm_dense_lowp_constant(int x_kind, int which);
 /* grad.timesBy(times), then the regulariser (GradientDescent.scala:53-87), in place, on the form toAuto
  * chose.  SKML_REG_L1 is l1Reg(grad, 0, reg_param) as written: v in [0, theta] -> Math.max(v - 0, 0),
  * v < 0 && v >= -theta -> Math.min(v - 0, 0) (Java's max / min: -0.0 becomes +0.0).  SKML_REG_L2 is
@@ -637,6 +666,14 @@ int skml_glm_validate_dense_f64(skml_ctx* ctx, const skml_glm_dense_data* data, 
                                 int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out);
 int skml_glm_validate_dense_f32(skml_ctx* ctx, const skml_glm_dense_data* data, int32_t loss_kind, const float* w_dev,
                                 int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out);
+/* skml_glm_validate_dense_* over an x stored as fp32, bf16 or fp16 (skml_glm_dense_lowp_data above): the
+ * bits of skml_glm_validate_dense_* on the widened array, and that struct's own refusals. */
+int skml_glm_validate_dense_lowp_f64(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int32_t loss_kind,
+                                     const double* w_dev, int32_t flags, double* pre_out, double* loss_out,
+                                     skml_valid_result* out);
+int skml_glm_validate_dense_lowp_f32(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int32_t loss_kind,
+                                     const float* w_dev, int32_t flags, double* pre_out, double* loss_out,
+                                     skml_valid_result* out);
 /* The AUC stage alone over n scores and labels on the device (n in [1, 2^31 - 1], 8-byte aligned):
  * *pos, *neg, *rank_sum and *nan_scores as above; order_out (optional, n int32 on the device, 4-byte
  * aligned, not overlapping the inputs) receives the sorted permutation: order_out[p] = the instance at

@@ -112,6 +112,24 @@ class GlmDenseData(C.Structure):
     _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("x", C.c_void_p), ("label", C.c_void_p)]
 
 
+# skml_glm_dense_lowp_data's x_kind (SKML_X_* of include/skml.h) by the torch type that stores x
+SKML_X_F32, SKML_X_BF16, SKML_X_F16 = 0, 1, 2
+X_KINDS = {torch.float32: SKML_X_F32, torch.bfloat16: SKML_X_BF16, torch.float16: SKML_X_F16}
+
+
+def glm_dense_lowp_constant(kind: int, name: str) -> int:
+    """skml_debug_glm_dense_lowp_constant: the shape constant `name` (GLM_DENSE_CONSTANTS) of the kernels over an
+    x of kind `kind` (SKML_X_*)."""
+    return lib.skml_debug_glm_dense_lowp_constant(kind, GLM_DENSE_CONSTANTS[name])
+
+
+class GlmDenseLowpData(C.Structure):
+    """skml_glm_dense_lowp_data (include/skml.h): rows of dim fp32, bf16 or fp16 values `pitch` elements apart,
+    every row on a 16-byte boundary, and the float64 labels on the device."""
+    _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("pitch", C.c_int64), ("x", C.c_void_p), ("label", C.c_void_p),
+                ("x_kind", C.c_int32)]
+
+
 class ValidResult(C.Structure):
     """skml_valid_result (include/skml.h): what one validation pass reads back."""
     _fields_ = [("loss", C.c_double), ("true_pos", C.c_int64), ("true_neg", C.c_int64), ("false_pos", C.c_int64),
@@ -212,6 +230,11 @@ _SIGS = {
     "skml_glm_validate_dense_f64": (C.c_int, [vp, C.POINTER(GlmDenseData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
     "skml_glm_validate_dense_f32": (C.c_int, [vp, C.POINTER(GlmDenseData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
     "skml_debug_glm_dense_constant": (C.c_int, [C.c_int]),
+    "skml_glm_gradient_dense_lowp_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_lowp_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_validate_dense_lowp_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_glm_validate_dense_lowp_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
+    "skml_debug_glm_dense_lowp_constant": (C.c_int, [C.c_int, C.c_int]),
     "skml_auc_rank_sum": (C.c_int, [vp, vp, vp, i64, vp, i64p, i64p, C.POINTER(C.c_uint64), i64p]),
     "skml_glm_seq_sum": (C.c_int, [vp, vp, i64, dblp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),

@@ -95,28 +95,24 @@ int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch,
         [&](const double* coef, unsigned long long* cnt) { return launch_glm_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
 }
 
-// gradient_x over dense instances: the same checks, then the same gradient_run.
-int gradient_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w,
-                     int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
-                     double* obj_loss_out) {
-    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
-    if (!d) return fail(SKML_E_ARG, "data is NULL");
-    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
-        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
-    size_t xb = 0;
-    if (!dense_bytes(d->rows, d->dim, &xb))
-        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
-    if (row0 < 0 || row0 >= d->rows) return fail(SKML_E_ARG, "row0=%lld outside [0, %lld)", (long long)row0, (long long)d->rows);
-    if (batch < 1 || batch > d->rows)
-        return fail(SKML_E_ARG, "batch=%lld outside [1, %lld]: a window wraps at most once", (long long)batch, (long long)d->rows);
+// What the dense entries share once rows, dim and the xb bytes of x are checked: gradient_x's other checks,
+// then the same gradient_run.
+template <typename Predict, typename PlusBy>
+int gradient_dense_rest(skml_ctx* c, int64_t rows, int64_t dim, const void* x, size_t xb, const double* label, int64_t row0,
+                        int64_t batch, int32_t loss_kind, const void* w, int wide, double* pre_out, double* coef_out,
+                        double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out, Predict predict,
+                        PlusBy plus_by) {
+    if (row0 < 0 || row0 >= rows) return fail(SKML_E_ARG, "row0=%lld outside [0, %lld)", (long long)row0, (long long)rows);
+    if (batch < 1 || batch > rows)
+        return fail(SKML_E_ARG, "batch=%lld outside [1, %lld]: a window wraps at most once", (long long)batch, (long long)rows);
     if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
         loss_kind != SKML_LOSS_L2_SQUARE)
         return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
-    const size_t bb = (size_t)batch * 8, db = (size_t)d->dim * 8;
-    const Range in[] = {{d->x, xb, "x"}, {d->label, (size_t)d->rows * 8, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
+    const size_t bb = (size_t)batch * 8, db = (size_t)dim * 8;
+    const Range in[] = {{x, xb, "x"}, {label, (size_t)rows * 8, "label"}, {w, (size_t)dim * (wide ? 8 : 4), "w"}};
     const Range out[] = {{pre_out, bb, "pre_out"}, {coef_out, bb, "coef_out"}, {loss_out, bb, "loss_out"}};
     const Range grad{grad_out, db, "grad_out"};
-    if (!d->x || !d->label || !w || !grad_out) return fail(SKML_E_ARG, "x, label, w or grad_out is NULL");
+    if (!x || !label || !w || !grad_out) return fail(SKML_E_ARG, "x, label, w or grad_out is NULL");
     if (!nnz_out || !obj_loss_out) return fail(SKML_E_ARG, "nnz_out or obj_loss_out is NULL");
     for (const Range& r : in)
         if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
@@ -133,10 +129,38 @@ int gradient_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, in
     if (overlap(out[0], out[1]) || overlap(out[0], out[2]) || overlap(out[1], out[2]))
         return fail(SKML_E_ARG, "pre_out, coef_out and loss_out overlap");
 
-    return gradient_run(
-        c, batch, coef_out, loss_out, nnz_out, obj_loss_out,
+    return gradient_run(c, batch, coef_out, loss_out, nnz_out, obj_loss_out, predict, plus_by);
+}
+
+// gradient_x over dense instances.
+int gradient_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w,
+                     int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
+                     double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    size_t xb = 0;
+    if (!dense_bytes(d->rows, d->dim, &xb))
+        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
+    return gradient_dense_rest(
+        c, d->rows, d->dim, d->x, xb, d->label, row0, batch, loss_kind, w, wide, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out,
         [&](double* coef, double* loss) { return launch_glm_dense_predict(c->stream, *d, row0, batch, loss_kind, w, wide, pre_out, coef, loss); },
         [&](const double* coef, unsigned long long* cnt) { return launch_glm_dense_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
+}
+
+// gradient_dense_x over an x stored as fp32, bf16 or fp16.
+int gradient_dense_lowp_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int64_t row0, int64_t batch, int32_t loss_kind,
+                          const void* w, int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                          int64_t* nnz_out, double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    size_t xb = 0;
+    if (const int st = dense_lowp_check(d, &xb)) return st;
+    return gradient_dense_rest(
+        c, d->rows, d->dim, d->x, xb, d->label, row0, batch, loss_kind, w, wide, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out,
+        [&](double* coef, double* loss) { return launch_glm_dense_lowp_predict(c->stream, *d, row0, batch, loss_kind, w, wide, pre_out, coef, loss); },
+        [&](const double* coef, unsigned long long* cnt) { return launch_glm_dense_lowp_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
 }
 
 int finish_x(skml_ctx* c, const int32_t* keys, bool kv, double* vals, int64_t n, int64_t dim, double times, int32_t reg_kind,
@@ -185,6 +209,32 @@ int skml_glm_gradient_dense_f32(skml_ctx* c, const skml_glm_dense_data* data, in
                                 const float* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
                                 int64_t* nnz_out, double* obj_loss_out) {
     return gradient_dense_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_glm_gradient_dense_lowp_f64(skml_ctx* c, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                     int32_t loss_kind, const double* w, double* pre_out, double* coef_out, double* loss_out,
+                                     double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_dense_lowp_x(c, data, row0, batch, loss_kind, w, 1, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_glm_gradient_dense_lowp_f32(skml_ctx* c, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                     int32_t loss_kind, const float* w, double* pre_out, double* coef_out, double* loss_out,
+                                     double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_dense_lowp_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_debug_glm_dense_lowp_constant(int x_kind, int which) {
+    const int e = lowp_elems_per_group(x_kind);
+    if (!e) return -1;
+    switch (which) {
+        case SKML_GLM_DENSE_C: return e == 4 ? LowpTile<4>::kC : LowpTile<8>::kC;
+        case SKML_GLM_DENSE_STRIDE: return e == 4 ? LowpTile<4>::kS : LowpTile<8>::kS;
+        case SKML_GLM_DENSE_U: return kLowpU;
+        case SKML_GLM_DENSE_V: return e == 4 ? LowpCols<4>::kV : LowpCols<8>::kV;
+        case SKML_GLM_DENSE_ROW_GROUP_AT: return (int)kLowpGroupAt;
+        case SKML_GLM_DENSE_COL_GROUP_AT: return (int)kLowpColGroupAt;
+        default: return -1;
+    }
 }
 
 int skml_debug_glm_dense_constant(int which) {

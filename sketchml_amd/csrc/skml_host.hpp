@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "skml_glm_dense_lowp.hpp"
 #include "skml_internal.h"
 #include "skml_sparse.h"
 
@@ -155,6 +156,24 @@ inline bool dense_bytes(int64_t rows, int64_t dim, size_t* bytes) {
     if (__builtin_mul_overflow(rows, dim, &n) || n > INT64_MAX / 8) return false;
     *bytes = (size_t)n * 8;
     return true;
+}
+
+// What the entries over a skml_glm_dense_lowp_data check of the struct before anything else: rows and dim, the
+// kind, the pitch rule, and *bytes of the rows * pitch elements of x.
+inline int dense_lowp_check(const skml_glm_dense_lowp_data* d, size_t* bytes) {
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    const int64_t e = lowp_elems_per_group(d->x_kind);
+    if (!e) return fail(SKML_E_ARG, "unknown x_kind %d", d->x_kind);
+    if (d->pitch < d->dim || d->pitch % e)
+        return fail(SKML_E_ARG, "pitch=%lld is below dim=%lld or leaves a row off a 16-byte boundary (a multiple of %lld elements)",
+                    (long long)d->pitch, (long long)d->dim, (long long)e);
+    if (((uintptr_t)d->x) % 16) return fail(SKML_E_ARG, "x must be 16-byte aligned");
+    int64_t n;
+    if (__builtin_mul_overflow(d->rows, d->pitch, &n) || n > INT64_MAX / (16 / e))
+        return fail(SKML_E_ARG, "rows=%lld times pitch=%lld elements do not fit an int64", (long long)d->rows, (long long)d->pitch);
+    *bytes = (size_t)n * (size_t)(16 / e);
+    return SKML_OK;
 }
 
 inline bool valid_payload_ptr(const void* p) { return p && (((uintptr_t)p) % 256 == 0); }

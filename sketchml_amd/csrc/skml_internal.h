@@ -295,6 +295,13 @@ hipError_t launch_glm_dense_plus_by(hipStream_t st, const skml_glm_dense_data& d
                                     const double* coef, double* g, unsigned long long* count);
 hipError_t launch_glm_dense_valid(hipStream_t st, const skml_glm_dense_data& d, int loss_kind, const void* w, int wide,
                                   double* pre, double* loss, unsigned long long* cnt);
+// ---- dense instances with x stored as fp32, bf16 or fp16 (skml_glm_dense_lowp.hip): the same three over d.x_kind ----
+hipError_t launch_glm_dense_lowp_predict(hipStream_t st, const skml_glm_dense_lowp_data& d, int64_t row0, int64_t batch,
+                                         int loss_kind, const void* w, int wide, double* pre, double* coef, double* loss);
+hipError_t launch_glm_dense_lowp_plus_by(hipStream_t st, const skml_glm_dense_lowp_data& d, int64_t row0, int64_t batch,
+                                         const double* coef, double* g, unsigned long long* count);
+hipError_t launch_glm_dense_lowp_valid(hipStream_t st, const skml_glm_dense_lowp_data& d, int loss_kind, const void* w, int wide,
+                                       double* pre, double* loss, unsigned long long* cnt);
 // *out = ((0.0 + x[0]) + x[1]) + ... + x[n - 1] by one wave
 hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out);
 // Scratch of the key-and-payload sort over n scores; the sorted permutation ends in idx_a.

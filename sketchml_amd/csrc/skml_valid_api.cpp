@@ -138,6 +138,31 @@ int validate_x(skml_ctx* c, const skml_glm_data* d, int32_t loss_kind, const voi
     });
 }
 
+// What the dense passes share once rows, dim and the xb bytes of x are checked: validate_x's other checks, then
+// the same validate_run.
+template <typename Launch>
+int validate_dense_rest(skml_ctx* c, int64_t rows, int64_t dim, const void* x, size_t xb, const double* label, int32_t loss_kind,
+                        const void* w, int wide, int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out,
+                        Launch launch) {
+    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
+        loss_kind != SKML_LOSS_L2_SQUARE)
+        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
+    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    const size_t rb = (size_t)rows * 8;
+    const Range in[] = {{x, xb, "x"}, {label, rb, "label"}, {w, (size_t)dim * (wide ? 8 : 4), "w"}};
+    const Range outs[] = {{pre_out, rb, "pre_out"}, {loss_out, rb, "loss_out"}};
+    if (!x || !label || !w) return fail(SKML_E_ARG, "x, label or w is NULL");
+    for (const Range& r : in)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    for (const Range& r : outs) {
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+        for (const Range& q : in)
+            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
+    }
+    if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
+    return validate_run(c, rows, label, flags, pre_out, loss_out, out, launch);
+}
+
 int validate_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int32_t loss_kind, const void* w, int wide, int32_t flags,
                      double* pre_out, double* loss_out, skml_valid_result* out) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -148,25 +173,23 @@ int validate_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int32_t loss_kin
     size_t xb = 0;
     if (!dense_bytes(d->rows, d->dim, &xb))
         return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
-    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
-        loss_kind != SKML_LOSS_L2_SQUARE)
-        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
-    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
-    const size_t rb = (size_t)d->rows * 8;
-    const Range in[] = {{d->x, xb, "x"}, {d->label, rb, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
-    const Range outs[] = {{pre_out, rb, "pre_out"}, {loss_out, rb, "loss_out"}};
-    if (!d->x || !d->label || !w) return fail(SKML_E_ARG, "x, label or w is NULL");
-    for (const Range& r : in)
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-    for (const Range& r : outs) {
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-        for (const Range& q : in)
-            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
-    }
-    if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
-    return validate_run(c, d->rows, d->label, flags, pre_out, loss_out, out, [&](double* pre, double* loss, unsigned long long* head) {
-        return launch_glm_dense_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
-    });
+    return validate_dense_rest(c, d->rows, d->dim, d->x, xb, d->label, loss_kind, w, wide, flags, pre_out, loss_out, out,
+                               [&](double* pre, double* loss, unsigned long long* head) {
+                                   return launch_glm_dense_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
+                               });
+}
+
+int validate_dense_lowp_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int32_t loss_kind, const void* w, int wide,
+                          int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (!out) return fail(SKML_E_ARG, "out is NULL");
+    size_t xb = 0;
+    if (const int st = dense_lowp_check(d, &xb)) return st;
+    return validate_dense_rest(c, d->rows, d->dim, d->x, xb, d->label, loss_kind, w, wide, flags, pre_out, loss_out, out,
+                               [&](double* pre, double* loss, unsigned long long* head) {
+                                   return launch_glm_dense_lowp_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
+                               });
 }
 
 }  // namespace
@@ -191,6 +214,16 @@ int skml_glm_validate_dense_f64(skml_ctx* c, const skml_glm_dense_data* data, in
 int skml_glm_validate_dense_f32(skml_ctx* c, const skml_glm_dense_data* data, int32_t loss_kind, const float* w, int32_t flags,
                                 double* pre_out, double* loss_out, skml_valid_result* out) {
     return validate_dense_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
+}
+
+int skml_glm_validate_dense_lowp_f64(skml_ctx* c, const skml_glm_dense_lowp_data* data, int32_t loss_kind, const double* w,
+                                     int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
+    return validate_dense_lowp_x(c, data, loss_kind, w, 1, flags, pre_out, loss_out, out);
+}
+
+int skml_glm_validate_dense_lowp_f32(skml_ctx* c, const skml_glm_dense_lowp_data* data, int32_t loss_kind, const float* w,
+                                     int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
+    return validate_dense_lowp_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
 }
 
 int skml_auc_rank_sum(skml_ctx* c, const double* scores, const double* labels, int64_t n, int32_t* order_out, int64_t* pos,

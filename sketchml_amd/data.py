@@ -6,7 +6,8 @@ A DataSet is the CSR of its sparse instances (row_ptr, col, val, label) plus the
 (skml_glm_data, include/skml.h).  A batch of DataSet.loopingRead is a window of consecutive rows, so
 the column order is built once, at first use, with a stable sort; nothing is sorted per batch.
 
-A DenseDataSet holds dense instances (format csv) as one row-major array (skml_glm_dense_data).
+A DenseDataSet holds dense instances (format csv) as one row-major array (skml_glm_dense_data), of
+float64 values or, with xDtype, of float32, bfloat16 or float16 values (skml_glm_dense_lowp_data).
 """
 from __future__ import annotations
 
@@ -79,7 +80,8 @@ class DataSet:
     and builds the column order there.  readIndex is loopingRead's cursor.
     """
 
-    dense = False  # the entries of include/skml.h that serve it: skml_glm_*_f64 / _f32
+    dense = False
+    entry = ""  # the entries of include/skml.h that serve it: skml_glm_<gradient | validate>_ + entry + f64 / f32
 
     def __init__(self, dim: int, device=None):
         self.dim = int(dim)
@@ -217,14 +219,31 @@ class DenseDataSet:
 
     DenseDataSet(dim) then add((label, values)) row by row, or fromRows / fromArray.  A row whose
     length is not dim is refused, where the reference's `require` or an array bound would throw.
+
+    xDtype = torch.float32, torch.bfloat16 or torch.float16 stores x in that type instead (a csv value
+    parsed to float32 gains nothing from 8 bytes): `x` is then a rows x pitch tensor of that type, the
+    rows padded to a multiple of 16 bytes (`pitch` elements, `x_kind` the SKML_X_* id), built with one
+    copy at first use.  A device tensor already of that type whose rows are 16-byte aligned (rows x
+    dim with dim a multiple of 16 bytes, or a [:, :dim] view of a wider such tensor) is taken as it
+    is; a wider input is rounded once, to nearest even, by torch's conversion.  The gradient and the
+    validation pass then give the bits of a float64 DenseDataSet over the widened values
+    (skml_glm_*_dense_lowp_*), and read a half, a quarter of the bytes.
     """
 
-    dense = True  # the entries of include/skml.h that serve it: skml_glm_*_dense_f64 / _f32
+    dense = True
 
-    def __init__(self, dim: int, device=None):
+    def __init__(self, dim: int, device=None, xDtype=None):
         self.dim = int(dim)
         if not 1 <= self.dim <= JAVA_INT_MAX:
             raise SketchMLException(f"dim={dim} outside [1, 2^31 - 1]")
+        if xDtype is not None and xDtype not in _lib.X_KINDS:
+            raise SketchMLException(f"xDtype={xDtype}: torch.float32, torch.bfloat16, torch.float16, or None for float64")
+        self.xDtype = xDtype
+        self.x_kind = _lib.X_KINDS.get(xDtype)  # None: float64
+        per16 = 16 // torch.empty(0, dtype=xDtype).element_size() if xDtype is not None else 1
+        self.pitch = -(-self.dim // per16) * per16
+        # the entries of include/skml.h that serve it: skml_glm_*_dense_f64 / _f32, or _dense_lowp_
+        self.entry = "dense_" if xDtype is None else "dense_lowp_"
         self.device = _device(device)
         self.readIndex = 0
         self._labels: list = []
@@ -233,16 +252,16 @@ class DenseDataSet:
         self._built = False
 
     @classmethod
-    def fromRows(cls, rows, dim: int, device=None) -> "DenseDataSet":
-        ds = cls(dim, device)
+    def fromRows(cls, rows, dim: int, device=None, xDtype=None) -> "DenseDataSet":
+        ds = cls(dim, device, xDtype)
         for ins in rows:
             ds.add(ins)
         return ds
 
     @classmethod
-    def fromArray(cls, x, label, dim: int, device=None) -> "DenseDataSet":
+    def fromArray(cls, x, label, dim: int, device=None, xDtype=None) -> "DenseDataSet":
         """x: rows * dim values (rows x dim, or flat and row-major); label: rows values."""
-        ds = cls(dim, device)
+        ds = cls(dim, device, xDtype)
         ds._arrays = (torch.as_tensor(x), torch.as_tensor(label))
         return ds
 
@@ -270,10 +289,25 @@ class DenseDataSet:
     window_rows = staticmethod(DataSet.window_rows)
 
     def loopingRead(self):
-        """(label, values) of the next instance, as a host float and list."""
+        """(label, values) of the next instance, as a host float and list (a narrow x widened exactly)."""
         r = self.take(1)
         self._build()
+        if self.xDtype is not None:
+            return float(self.label[r]), self.x[r, :self.dim].double().tolist()
         return float(self.label[r]), self.x[r * self.dim:(r + 1) * self.dim].tolist()
+
+    def _narrow(self, x: torch.Tensor, rows: int) -> torch.Tensor:
+        """x as rows x pitch values of xDtype on the device, every row on a 16-byte boundary."""
+        x = x.to(device=self.device).reshape(rows, self.dim)
+        size = x.element_size()
+        if (x.dtype == self.xDtype and x.stride(1) == 1 and x.stride(0) >= self.dim and (x.stride(0) * size) % 16 == 0
+                and x.data_ptr() % 16 == 0
+                and (x.storage_offset() + rows * x.stride(0)) * size <= x.untyped_storage().nbytes()):  # the last row's pad exists
+            self.pitch = x.stride(0)
+            return x  # as it is: a view of rows x pitch values
+        full = torch.zeros(rows, self.pitch, dtype=self.xDtype, device=self.device)
+        full[:, :self.dim] = x  # the one rounding of a wider input
+        return full
 
     def _build(self) -> None:
         if self._built:
@@ -283,22 +317,30 @@ class DenseDataSet:
         else:
             x = torch.tensor(self._values, dtype=torch.float64)
             label = torch.tensor(self._labels, dtype=torch.float64)
-        x = x.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
         label = label.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
         rows = int(label.numel())
         if rows < 1 or rows > JAVA_INT_MAX:
             raise SketchMLException(f"{rows} instances: outside [1, 2^31 - 1]")
         if x.numel() != rows * self.dim:
             raise SketchMLException(f"{x.numel()} values for {rows} instances of {self.dim} features")
+        if self.xDtype is not None:
+            x = self._narrow(x, rows)
+        else:
+            x = x.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
         self.x, self.label, self.rows = x, label, rows
         self._arrays = (x, label)
         self._labels = self._values = None
         self._built = True
 
-    def glm_data(self) -> _lib.GlmDenseData:
-        """The skml_glm_dense_data of this data set; the tensors stay owned by it."""
+    def glm_data(self):
+        """The skml_glm_dense_data of this data set, or its skml_glm_dense_lowp_data with an xDtype; the
+        tensors stay owned by it."""
         self._build()
-        d = _lib.GlmDenseData()
+        if self.xDtype is not None:
+            d = _lib.GlmDenseLowpData()
+            d.pitch, d.x_kind = self.pitch, self.x_kind
+        else:
+            d = _lib.GlmDenseData()
         d.rows, d.dim = self.rows, self.dim
         d.x, d.label = C.c_void_p(self.x.data_ptr()).value, C.c_void_p(self.label.data_ptr()).value
         return d

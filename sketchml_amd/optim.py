@@ -53,7 +53,7 @@ def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, w
            "loss": torch.empty(batch, dtype=torch.float64, device=dev),
            "pre": torch.empty(batch, dtype=torch.float64, device=dev) if want_pre else None}
     nnz, obj = C.c_int64(), C.c_double()
-    fn = getattr(_lib.lib, "skml_glm_gradient_" + ("dense_" if dataSet.dense else "") +
+    fn = getattr(_lib.lib, "skml_glm_gradient_" + dataSet.entry +
                  ("f64" if weight.dtype == torch.float64 else "f32"))
     check(fn(get_context(dev).handle, C.byref(data), int(row0), int(batch), int(loss.kind), _ptr(weight), _ptr(out["pre"]),
              _ptr(out["coef"]), _ptr(out["loss"]), _ptr(out["grad"]), C.byref(nnz), C.byref(obj)), "glm_gradient")

@@ -99,7 +99,7 @@ def _validate(weights: torch.Tensor, validData, loss, order: str, auc: bool) -> 
     pre = torch.empty(validData.rows, dtype=torch.float64, device=dev)
     per = torch.empty(validData.rows, dtype=torch.float64, device=dev)
     res = _lib.ValidResult()
-    fn = getattr(_lib.lib, "skml_glm_validate_" + ("dense_" if validData.dense else "") +
+    fn = getattr(_lib.lib, "skml_glm_validate_" + validData.entry +
                  ("f64" if weights.dtype == torch.float64 else "f32"))
     check(fn(get_context(dev).handle, C.byref(data), int(loss.kind), _ptr(weights), flags, _ptr(pre), _ptr(per), C.byref(res)),
           "glm_validate")

@@ -600,6 +600,36 @@ int skml_glm_gradient_dense_lowp_f32(skml_ctx* ctx, const skml_glm_dense_lowp_da
 /* The shape constants of these kernels (csrc/skml_glm_dense_lowp.hpp) for an x of kind x_kind, `which` as
  * SKML_GLM_DENSE_* above (STRIDE in dwords); -1 for any other x_kind or `which`. */
 int skml_debug_glm_dense_lowp_constant(int x_kind, int which);
+/* The four dense gradients above in the blocked summation order: opt-in twins for a caller who needs a
+ * deterministic gradient at memory speed, not the bits of the reference's sequential `+=`.  Arguments, outputs,
+ * NULL rules, refusals, the single synchronisation, stream behaviour and timing ids are the sequential twin's
+ * (the partial sums and their reduction are timed under SKML_K_GLM_PLUS_BY).  What changes is the order of the
+ * two sums, all in double over the exactly widened x, each product fused into its add:
+ *   pre_j       a sum over all dim columns: L lanes (8 .. 64) share a row and add their own 16-byte groups,
+ *               then a fixed butterfly over the lanes (and, for a long row of a small batch, over S waves)
+ *   grad_out[k] a sum over the batch rows: NB blocks of RB consecutive batch positions, each from +0.0 in
+ *               order, then the NB partial sums from +0.0 in block order
+ * The order is a function of batch, dim, the storage type of x and compile-time constants (row0 enters only
+ * through the window), never of the device, atomics or timing: the same call gives the same bits on every
+ * run.  coef_j, loss_j, objLoss and toAuto's count are computed as above from this pre_j and this grad_out.  NaN
+ * and Inf take part as in any IEEE sum; pad elements of a pitched row reach no sum.  The partial sums live in
+ * the context's staging buffer (at most 1 / 32 of the window's bytes of x).  skml_glm_finish_* serves the gradient unchanged. */
+int skml_glm_gradient_dense_blocked_f64(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                        int32_t loss_kind, const double* w_dev, double* pre_out, double* coef_out,
+                                        double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_blocked_f32(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                        int32_t loss_kind, const float* w_dev, double* pre_out, double* coef_out,
+                                        double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_lowp_blocked_f64(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                             int32_t loss_kind, const double* w_dev, double* pre_out, double* coef_out,
+                                             double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_lowp_blocked_f32(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                             int32_t loss_kind, const float* w_dev, double* pre_out, double* coef_out,
+                                             double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+/* The plan of such a call (csrc/skml_glm_dense_blocked.hpp; host arithmetic only) for an x of x_bytes (8, 4 or
+ * 2) per element: out = lanes per row L, waves per row S, rows in flight per wave, RB, NB, bytes of partial
+ * sums (0 with NB = 1).  -1 for any other x_bytes, or batch or dim outside [1, 2^31 - 1]. */
+int skml_debug_glm_dense_blocked_plan(int x_bytes, int64_t batch, int64_t dim, int64_t out[6]);
 /* grad.timesBy(times), then the regulariser (GradientDescent.scala:53-87), in place, on the form toAuto
  * chose.  SKML_REG_L1 is l1Reg(grad, 0, reg_param) as written: v in [0, theta] -> Math.max(v - 0, 0),
  * v < 0 && v >= -theta -> Math.min(v - 0, 0) (Java's max / min: -0.0 becomes +0.0).  SKML_REG_L2 is

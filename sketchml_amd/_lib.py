@@ -130,6 +130,13 @@ class GlmDenseLowpData(C.Structure):
                 ("x_kind", C.c_int32)]
 
 
+def glm_dense_blocked_plan(x_bytes: int, batch: int, dim: int):
+    """skml_debug_glm_dense_blocked_plan: (lanes per row, waves per row, rows in flight per wave, RB, NB, bytes of
+    partial sums) of the blocked gradient over an x of x_bytes per element; None for bad arguments."""
+    out = (C.c_int64 * 6)()
+    return tuple(out) if lib.skml_debug_glm_dense_blocked_plan(int(x_bytes), int(batch), int(dim), out) == 0 else None
+
+
 class ValidResult(C.Structure):
     """skml_valid_result (include/skml.h): what one validation pass reads back."""
     _fields_ = [("loss", C.c_double), ("true_pos", C.c_int64), ("true_neg", C.c_int64), ("false_pos", C.c_int64),
@@ -235,6 +242,11 @@ _SIGS = {
     "skml_glm_validate_dense_lowp_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
     "skml_glm_validate_dense_lowp_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i32, vp, i32, vp, vp, C.POINTER(ValidResult)]),
     "skml_debug_glm_dense_lowp_constant": (C.c_int, [C.c_int, C.c_int]),
+    "skml_glm_gradient_dense_blocked_f64": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_blocked_f32": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_lowp_blocked_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_lowp_blocked_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_debug_glm_dense_blocked_plan": (C.c_int, [C.c_int, i64, i64, i64p]),
     "skml_auc_rank_sum": (C.c_int, [vp, vp, vp, i64, vp, i64p, i64p, C.POINTER(C.c_uint64), i64p]),
     "skml_glm_seq_sum": (C.c_int, [vp, vp, i64, dblp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),

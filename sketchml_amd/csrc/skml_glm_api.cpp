@@ -3,6 +3,7 @@
 // the arrays the caller does not keep, the launches of skml_glm.hip and the one read-back of
 // toAuto's count and objLoss.
 #include "skml_glm_dense.hpp"
+#include "skml_glm_dense_blocked.hpp"
 #include "skml_host.hpp"
 
 using namespace skml;
@@ -163,6 +164,55 @@ int gradient_dense_lowp_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int64_
         [&](const double* coef, unsigned long long* cnt) { return launch_glm_dense_lowp_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
 }
 
+// The dense entries in the blocked summation order (skml_glm_dense_blocked.hip), once the struct is checked:
+// gradient_dense_rest's checks come first, as for the sequential twins, and nothing is touched before them.
+// The partial sums of the column sum live in the context's staging buffer, grown inside plus_by: every use of
+// that buffer is ordered on the context's stream, and gradient_run's own workspace is not moved under it.
+int gradient_dense_blocked_rest(skml_ctx* c, const GlmBlockedX& bx, int x_bytes, size_t xb, int64_t row0, int64_t batch,
+                                int32_t loss_kind, const void* w, int wide, double* pre_out, double* coef_out, double* loss_out,
+                                double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_dense_rest(
+        c, bx.rows, bx.dim, bx.x, xb, bx.label, row0, batch, loss_kind, w, wide, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out,
+        [&](double* coef, double* loss) { return launch_glm_dense_blocked_predict(c->stream, bx, row0, batch, loss_kind, w, wide, pre_out, coef, loss); },
+        [&](const double* coef, unsigned long long* cnt) {
+            BlkPlan plan;
+            if (!blk_plan(x_bytes, batch, bx.dim, &plan)) return hipErrorInvalidValue;
+            const size_t need = (size_t)plan.ws_bytes;
+            if (need && reserve(c, c->stage, need, need + need / 4, "the blocked gradient's partial sums")) return hipErrorOutOfMemory;
+            return launch_glm_dense_blocked_plus_by(c->stream, bx, row0, batch, coef, need ? static_cast<double*>(c->stage.p) : nullptr,
+                                                    grad_out, cnt);
+        });
+}
+
+// gradient_dense_x in the blocked order.
+int gradient_dense_blocked_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, int64_t batch, int32_t loss_kind,
+                             const void* w, int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                             int64_t* nnz_out, double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    size_t xb = 0;
+    if (!dense_bytes(d->rows, d->dim, &xb))
+        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
+    const GlmBlockedX bx{d->rows, d->dim, d->dim, d->x, d->label, kBlkXF64};
+    return gradient_dense_blocked_rest(c, bx, 8, xb, row0, batch, loss_kind, w, wide, pre_out, coef_out, loss_out, grad_out, nnz_out,
+                                       obj_loss_out);
+}
+
+// gradient_dense_lowp_x in the blocked order.
+int gradient_dense_lowp_blocked_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int64_t row0, int64_t batch, int32_t loss_kind,
+                                  const void* w, int wide, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                  int64_t* nnz_out, double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    size_t xb = 0;
+    if (const int st = dense_lowp_check(d, &xb)) return st;
+    const GlmBlockedX bx{d->rows, d->dim, d->pitch, d->x, d->label, d->x_kind};
+    return gradient_dense_blocked_rest(c, bx, 16 / lowp_elems_per_group(d->x_kind), xb, row0, batch, loss_kind, w, wide, pre_out, coef_out,
+                                       loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
 int finish_x(skml_ctx* c, const int32_t* keys, bool kv, double* vals, int64_t n, int64_t dim, double times, int32_t reg_kind,
              double reg_param, const void* w, int32_t w_fp32) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -221,6 +271,29 @@ int skml_glm_gradient_dense_lowp_f32(skml_ctx* c, const skml_glm_dense_lowp_data
                                      int32_t loss_kind, const float* w, double* pre_out, double* coef_out, double* loss_out,
                                      double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
     return gradient_dense_lowp_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+#define SKML_BLOCKED_ENTRY(name, data_t, w_t, fn, wide)                                                                              \
+    int name(skml_ctx* c, const data_t* data, int64_t row0, int64_t batch, int32_t loss_kind, const w_t* w, double* pre_out,         \
+             double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out) {                         \
+        return fn(c, data, row0, batch, loss_kind, w, wide, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);           \
+    }
+SKML_BLOCKED_ENTRY(skml_glm_gradient_dense_blocked_f64, skml_glm_dense_data, double, gradient_dense_blocked_x, 1)
+SKML_BLOCKED_ENTRY(skml_glm_gradient_dense_blocked_f32, skml_glm_dense_data, float, gradient_dense_blocked_x, 0)
+SKML_BLOCKED_ENTRY(skml_glm_gradient_dense_lowp_blocked_f64, skml_glm_dense_lowp_data, double, gradient_dense_lowp_blocked_x, 1)
+SKML_BLOCKED_ENTRY(skml_glm_gradient_dense_lowp_blocked_f32, skml_glm_dense_lowp_data, float, gradient_dense_lowp_blocked_x, 0)
+#undef SKML_BLOCKED_ENTRY
+
+int skml_debug_glm_dense_blocked_plan(int x_bytes, int64_t batch, int64_t dim, int64_t out[6]) {
+    BlkPlan p;
+    if (!out || !blk_plan(x_bytes, batch, dim, &p)) return -1;
+    out[0] = p.lanes;
+    out[1] = p.split;
+    out[2] = p.rows_in_flight;
+    out[3] = p.rb;
+    out[4] = p.nb;
+    out[5] = p.ws_bytes;
+    return 0;
 }
 
 int skml_debug_glm_dense_lowp_constant(int x_kind, int which) {

@@ -302,6 +302,19 @@ hipError_t launch_glm_dense_lowp_plus_by(hipStream_t st, const skml_glm_dense_lo
                                          const double* coef, double* g, unsigned long long* count);
 hipError_t launch_glm_dense_lowp_valid(hipStream_t st, const skml_glm_dense_lowp_data& d, int loss_kind, const void* w, int wide,
                                        double* pre, double* loss, unsigned long long* cnt);
+// ---- dense instances in the blocked summation order (skml_glm_dense_blocked.hip): either dense struct as one ----
+constexpr int kBlkXF64 = -1;  // x_kind of a double x, beside SKML_X_*
+struct GlmBlockedX {
+    int64_t rows, dim, pitch;  // pitch = dim for a double x
+    const void* x;
+    const double* label;
+    int x_kind;
+};
+hipError_t launch_glm_dense_blocked_predict(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, int loss_kind,
+                                            const void* w, int wide, double* pre, double* coef, double* loss);
+// partial: blk_plan's ws_bytes (skml_glm_dense_blocked.hpp), may be null when that is 0
+hipError_t launch_glm_dense_blocked_plus_by(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, const double* coef,
+                                            double* partial, double* g, unsigned long long* count);
 // *out = ((0.0 + x[0]) + x[1]) + ... + x[n - 1] by one wave
 hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out);
 // Scratch of the key-and-payload sort over n scores; the sorted permutation ends in idx_a.

@@ -24,7 +24,7 @@ import torch
 from .exceptions import SketchMLException
 from .gradient import DenseDoubleGradient, Kind, compress
 from .loss import L2HingeLoss, L2LogLoss, L2SquareLoss
-from .optim import Adam
+from .optim import Adam, _order_infix
 from .validation import calLossPrecision
 
 ML_LOGISTIC_REGRESSION = "LogisticRegression"
@@ -93,13 +93,16 @@ class GeneralizedLinearModel:
 
     name = ""
 
-    def __init__(self, conf: MLConf, trainData, validData, device=None, seed: int = 0, hashSeed: int = 0):
+    def __init__(self, conf: MLConf, trainData, validData, device=None, seed: int = 0, hashSeed: int = 0,
+                 gradientOrder: str = "sequential"):
         if conf.workerNum != 1:
             raise SketchMLException(f"workerNum={conf.workerNum}: the multi-worker training loop is not built here "
                                     f"(DESIGN.md section 9); one worker trains on this device")
         self.conf, self.trainData, self.validData = conf, trainData, validData
         self.device = torch.device(device) if device is not None else trainData.device
         self.seed, self.hashSeed = int(seed), int(hashSeed)
+        _order_infix(trainData, gradientOrder)  # a misspelt order, or "blocked" over a sparse DataSet, is refused here
+        self.gradientOrder = gradientOrder  # optim.batch_gradient's order; the validation pass keeps the sequential dot
         self.weights = self.optimizer = self.loss = self.gradient = None
         self.lastValidation = None
 
@@ -142,7 +145,7 @@ class GeneralizedLinearModel:
 
     def computeGradient(self, epoch: int, batch: int) -> float:
         grad, batchSize, objLoss, regLoss = self.optimizer.miniBatchGradientDescent(self.weights, self.trainData, self.loss,
-                                                                                    sequentialLoss=True)
+                                                                                    sequentialLoss=True, order=self.gradientOrder)
         self.gradient = grad
         return objLoss / batchSize + regLoss / self.conf.workerNum
 

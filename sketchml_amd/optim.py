@@ -39,11 +39,29 @@ def _gradient_values(values) -> torch.Tensor:
     return as_device_f32(x) if x.dtype in LOWP_DTYPES else x
 
 
-def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, want_pre: bool = False):
+ORDERS = ("sequential", "blocked")
+
+
+def _order_infix(dataSet, order: str) -> str:
+    """"" for the reference's sequential sums; "blocked_" for the blocked order, which only the dense entries have."""
+    if order not in ORDERS:
+        raise SketchMLException(f"order={order!r}: one of {ORDERS}")
+    if order == "sequential":
+        return ""
+    if not getattr(dataSet, "dense", False):
+        raise SketchMLException("order='blocked' over a sparse DataSet is not built here: a data.DenseDataSet has it")
+    return "blocked_"
+
+
+def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, want_pre: bool = False,
+                   order: str = "sequential"):
     """skml_glm_gradient_*: the loop of miniBatchGradientDescent over the rows (row0 + j) mod size,
     j < batch, of a data.DataSet, or of a data.DenseDataSet (skml_glm_gradient_dense_*).  Returns a dict of float64 device tensors and two host scalars:
     grad (dim values, unscaled), coef (-1.0 * loss.grad per instance), loss (per instance), pre (when
-    asked for), nnz (toAuto's count of |grad| > 1e-8) and objLoss."""
+    asked for), nnz (toAuto's count of |grad| > 1e-8) and objLoss.  order="blocked" (a DenseDataSet only) takes
+    skml_glm_gradient_dense_*blocked_*: the same sums in a fixed blocked order, deterministic and at memory
+    speed, not the bits of the reference's sequential `+=`."""
+    infix = _order_infix(dataSet, order)
     dev = weight.device
     if dataSet.device != dev:
         raise SketchMLException(f"the data set lives on {dataSet.device}, the weight on {dev}")
@@ -53,7 +71,7 @@ def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, w
            "loss": torch.empty(batch, dtype=torch.float64, device=dev),
            "pre": torch.empty(batch, dtype=torch.float64, device=dev) if want_pre else None}
     nnz, obj = C.c_int64(), C.c_double()
-    fn = getattr(_lib.lib, "skml_glm_gradient_" + dataSet.entry +
+    fn = getattr(_lib.lib, "skml_glm_gradient_" + dataSet.entry + infix +
                  ("f64" if weight.dtype == torch.float64 else "f32"))
     check(fn(get_context(dev).handle, C.byref(data), int(row0), int(batch), int(loss.kind), _ptr(weight), _ptr(out["pre"]),
              _ptr(out["coef"]), _ptr(out["loss"]), _ptr(out["grad"]), C.byref(nnz), C.byref(obj)), "glm_gradient")
@@ -87,13 +105,15 @@ class GradientDescent:
         self.batch = 0
         self.batchNum = float(int(math.ceil(1.0 / batchSpRatio)))  # GradientDescent.scala:21
 
-    def miniBatchGradientDescent(self, weight: torch.Tensor, dataSet, loss, sequentialLoss: bool = False):
+    def miniBatchGradientDescent(self, weight: torch.Tensor, dataSet, loss, sequentialLoss: bool = False,
+                                 order: str = "sequential"):
         """GradientDescent.scala:23-51: (grad, batchSize, objLoss, regLoss) of the next
         (size * batchSpRatio).toInt instances of dataSet.loopingRead.  grad is toAuto's choice, a
         DenseDoubleGradient or a SparseDoubleGradient of float64 device tensors, scaled by
         1.0 / batchSize and regularised.  objLoss is a fixed-shape device sum of the per-instance
         losses, which stay in self.lastLoss; with sequentialLoss it is their sum in batch order
-        (skml_glm_seq_sum), the reference's `objLoss += ...` bit for bit given the losses."""
+        (skml_glm_seq_sum), the reference's `objLoss += ...` bit for bit given the losses.  order: batch_gradient's."""
+        _order_infix(dataSet, order)  # refused before the data set's read index moves
         batchSize = int(dataSet.size * self.batchSpRatio)
         if batchSize == 0 or self.batchSpRatio > 1:
             raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
@@ -101,7 +121,7 @@ class GradientDescent:
         self._check_weight(weight)
         if dataSet.dim != self.dim:
             raise SketchMLException(f"the data set has {dataSet.dim} features, the optimiser {self.dim}")
-        out = batch_gradient(weight, dataSet, dataSet.take(batchSize), batchSize, loss)
+        out = batch_gradient(weight, dataSet, dataSet.take(batchSize), batchSize, loss, order=order)
         self.lastLoss = out["loss"]
         if auto_dense(out["nnz"], self.dim):
             grad = DenseDoubleGradient(self.dim, out["grad"])

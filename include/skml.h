@@ -630,6 +630,38 @@ int skml_glm_gradient_dense_lowp_blocked_f32(skml_ctx* ctx, const skml_glm_dense
  * 2) per element: out = lanes per row L, waves per row S, rows in flight per wave, RB, NB, bytes of partial
  * sums (0 with NB = 1).  -1 for any other x_bytes, or batch or dim outside [1, 2^31 - 1]. */
 int skml_debug_glm_dense_blocked_plan(int x_bytes, int64_t batch, int64_t dim, int64_t out[6]);
+/* skml_glm_gradient_* over the same skml_glm_data in the segmented summation order: opt-in twins for a caller
+ * who needs a deterministic sparse gradient at memory speed, not the bits of the reference's sequential `+=`.
+ * Arguments, outputs, NULL rules, refusals, the single synchronisation, stream behaviour and timing ids are the
+ * sequential twin's (the tile pass, the wide pass and the slice reduction are timed under SKML_K_GLM_PLUS_BY).
+ * pre_j, coef_j, loss_j and objLoss are the sequential entry's bits.  What changes is the order of grad_out[k],
+ * and with it toAuto's count.  Let e_0 .. e_{m-1} be feature k's entries inside the window in batch order (the
+ * rows [row0, rows) first, then the wrapped rows); every product val * coef_j is rounded, then added:
+ *   m = 0          +0.0
+ *   m <= M_SEQ     from +0.0 in that order: the sequential entry's grad_out[k] bit for bit
+ *   m >  M_SEQ     lane l of a 64-lane wave adds, from +0.0 and in ascending p, the entries with p mod 64 == l;
+ *                  the 64 lane sums are joined by a fixed xor butterfly (distances 32, 16, 8, 4, 2, 1)
+ *   m >= SPLIT_AT  the entries are first cut into NS = ceil(m / SLICE) consecutive slices of SLICE entries (the
+ *                  last shorter); one wave sums each slice by the rule above, and the NS slice sums are added
+ *                  from +0.0 in slice order
+ * The order is a function of m and compile-time constants, never of the device, atomics or timing: the same call
+ * gives the same bits on every run.  No floating-point atomic anywhere.  NaN and Inf take part as in any IEEE
+ * sum; an entry whose row or batch position is out of range is skipped.  The list of wide columns and the slice
+ * sums live in the context's staging buffer (sized from dim and nnz alone).  skml_glm_finish_* serves the
+ * gradient unchanged. */
+int skml_glm_gradient_segmented_f64(skml_ctx* ctx, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                    const double* w_dev, double* pre_out, double* coef_out, double* loss_out,
+                                    double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_segmented_f32(skml_ctx* ctx, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                    const float* w_dev, double* pre_out, double* coef_out, double* loss_out,
+                                    double* grad_out, int64_t* nnz_out, double* obj_loss_out);
+/* The constants of that order and of its kernels (csrc/skml_glm_segmented.hpp), for the tests and the benchmark
+ * that place their shapes around them; -1 for any other `which`. */
+#define SKML_GLM_SEG_M_SEQ 0    /* window entries up to which a column is summed in batch order */
+#define SKML_GLM_SEG_SPLIT_AT 1 /* window entries from which a column is cut into slices */
+#define SKML_GLM_SEG_SLICE 2    /* window entries of a slice */
+#define SKML_GLM_SEG_TILE 3     /* features of one wave's tile of the tile pass */
+int skml_debug_glm_segmented_constant(int which);
 /* grad.timesBy(times), then the regulariser (GradientDescent.scala:53-87), in place, on the form toAuto
  * chose.  SKML_REG_L1 is l1Reg(grad, 0, reg_param) as written: v in [0, theta] -> Math.max(v - 0, 0),
  * v < 0 && v >= -theta -> Math.min(v - 0, 0) (Java's max / min: -0.0 becomes +0.0).  SKML_REG_L2 is

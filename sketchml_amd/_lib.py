@@ -107,6 +107,14 @@ def glm_dense_constant(name: str) -> int:
     return lib.skml_debug_glm_dense_constant(GLM_DENSE_CONSTANTS[name])
 
 
+# skml_debug_glm_segmented_constant's ids (SKML_GLM_SEG_* of include/skml.h)
+GLM_SEGMENTED_CONSTANTS = {"M_SEQ": 0, "SPLIT_AT": 1, "SLICE": 2, "TILE": 3}
+
+
+def glm_segmented_constant(name: str) -> int:
+    return lib.skml_debug_glm_segmented_constant(GLM_SEGMENTED_CONSTANTS[name])
+
+
 class GlmDenseData(C.Structure):
     """skml_glm_dense_data (include/skml.h): rows * dim doubles, row-major, and the labels on the device."""
     _fields_ = [("rows", C.c_int64), ("dim", C.c_int64), ("x", C.c_void_p), ("label", C.c_void_p)]
@@ -247,6 +255,9 @@ _SIGS = {
     "skml_glm_gradient_dense_lowp_blocked_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_glm_gradient_dense_lowp_blocked_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_debug_glm_dense_blocked_plan": (C.c_int, [C.c_int, i64, i64, i64p]),
+    "skml_glm_gradient_segmented_f64": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_segmented_f32": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_debug_glm_segmented_constant": (C.c_int, [C.c_int]),
     "skml_auc_rank_sum": (C.c_int, [vp, vp, vp, i64, vp, i64p, i64p, C.POINTER(C.c_uint64), i64p]),
     "skml_glm_seq_sum": (C.c_int, [vp, vp, i64, dblp]),
     "skml_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),

@@ -4,6 +4,7 @@
 // toAuto's count and objLoss.
 #include "skml_glm_dense.hpp"
 #include "skml_glm_dense_blocked.hpp"
+#include "skml_glm_segmented.hpp"
 #include "skml_host.hpp"
 
 using namespace skml;
@@ -49,9 +50,11 @@ int gradient_run(skml_ctx* c, int64_t batch, double* coef_out, double* loss_out,
     return SKML_OK;
 }
 
+// segmented: the column sum of skml_glm_segmented.hip in place of k_glm_plus_by; its work list and partial
+// sums live in the context's staging, grown inside plus_by as the blocked order's are.
 int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch, int32_t loss_kind, const void* w, int wide,
                double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
-               double* obj_loss_out) {
+               double* obj_loss_out, bool segmented = false) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
     if (!d) return fail(SKML_E_ARG, "data is NULL");
     if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax || d->nnz < 0)
@@ -93,7 +96,12 @@ int gradient_x(skml_ctx* c, const skml_glm_data* d, int64_t row0, int64_t batch,
         [&](double* coef, double* loss) {
             return launch_glm_predict(c->stream, *d, row0, batch, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre_out, coef, loss);
         },
-        [&](const double* coef, unsigned long long* cnt) { return launch_glm_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt); });
+        [&](const double* coef, unsigned long long* cnt) {
+            if (!segmented) return launch_glm_plus_by(c->stream, *d, row0, batch, coef, grad_out, cnt);
+            const size_t need = (size_t)seg_stage_bytes(d->dim, d->nnz);
+            if (reserve(c, c->stage, need, need + need / 4, "the segmented gradient's work list")) return hipErrorOutOfMemory;
+            return launch_glm_segmented_plus_by(c->stream, *d, row0, batch, coef, c->stage.p, grad_out, cnt);
+        });
 }
 
 // What the dense entries share once rows, dim and the xb bytes of x are checked: gradient_x's other checks,
@@ -271,6 +279,28 @@ int skml_glm_gradient_dense_lowp_f32(skml_ctx* c, const skml_glm_dense_lowp_data
                                      int32_t loss_kind, const float* w, double* pre_out, double* coef_out, double* loss_out,
                                      double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
     return gradient_dense_lowp_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
+int skml_glm_gradient_segmented_f64(skml_ctx* c, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                    const double* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                    int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_x(c, data, row0, batch, loss_kind, w, 1, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out, true);
+}
+
+int skml_glm_gradient_segmented_f32(skml_ctx* c, const skml_glm_data* data, int64_t row0, int64_t batch, int32_t loss_kind,
+                                    const float* w, double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                    int64_t* nnz_out, double* obj_loss_out) {
+    return gradient_x(c, data, row0, batch, loss_kind, w, 0, pre_out, coef_out, loss_out, grad_out, nnz_out, obj_loss_out, true);
+}
+
+int skml_debug_glm_segmented_constant(int which) {
+    switch (which) {
+        case SKML_GLM_SEG_M_SEQ: return kSegMSeq;
+        case SKML_GLM_SEG_SPLIT_AT: return kSegSplitAt;
+        case SKML_GLM_SEG_SLICE: return kSegSlice;
+        case SKML_GLM_SEG_TILE: return kSegTile;
+        default: return -1;
+    }
 }
 
 #define SKML_BLOCKED_ENTRY(name, data_t, w_t, fn, wide)                                                                              \

@@ -315,6 +315,10 @@ hipError_t launch_glm_dense_blocked_predict(hipStream_t st, const GlmBlockedX& d
 // partial: blk_plan's ws_bytes (skml_glm_dense_blocked.hpp), may be null when that is 0
 hipError_t launch_glm_dense_blocked_plus_by(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, const double* coef,
                                             double* partial, double* g, unsigned long long* count);
+// ---- the sparse column sum in the segmented summation order (skml_glm_segmented.hip) ----
+// stage: seg_stage_bytes(d.dim, d.nnz) bytes (skml_glm_segmented.hpp) that no other work on st uses
+hipError_t launch_glm_segmented_plus_by(hipStream_t st, const skml_glm_data& d, int64_t row0, int64_t batch, const double* coef,
+                                        void* stage, double* g, unsigned long long* count);
 // *out = ((0.0 + x[0]) + x[1]) + ... + x[n - 1] by one wave
 hipError_t launch_glm_seq_sum(hipStream_t st, const double* x, int64_t n, double* out);
 // Scratch of the key-and-payload sort over n scores; the sorted permutation ends in idx_a.

@@ -101,7 +101,7 @@ class GeneralizedLinearModel:
         self.conf, self.trainData, self.validData = conf, trainData, validData
         self.device = torch.device(device) if device is not None else trainData.device
         self.seed, self.hashSeed = int(seed), int(hashSeed)
-        _order_infix(trainData, gradientOrder)  # a misspelt order, or "blocked" over a sparse DataSet, is refused here
+        _order_infix(trainData, gradientOrder)  # a misspelt order, or one the data set's layout does not have, is refused here
         self.gradientOrder = gradientOrder  # optim.batch_gradient's order; the validation pass keeps the sequential dot
         self.weights = self.optimizer = self.loss = self.gradient = None
         self.lastValidation = None

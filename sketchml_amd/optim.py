@@ -39,18 +39,23 @@ def _gradient_values(values) -> torch.Tensor:
     return as_device_f32(x) if x.dtype in LOWP_DTYPES else x
 
 
-ORDERS = ("sequential", "blocked")
+ORDERS = ("sequential", "blocked", "segmented")
 
 
 def _order_infix(dataSet, order: str) -> str:
-    """"" for the reference's sequential sums; "blocked_" for the blocked order, which only the dense entries have."""
+    """"" for the reference's sequential sums; "blocked_" for the blocked order, which only the dense entries have;
+    "segmented_" for the segmented order, which only the sparse entries have."""
     if order not in ORDERS:
         raise SketchMLException(f"order={order!r}: one of {ORDERS}")
     if order == "sequential":
         return ""
-    if not getattr(dataSet, "dense", False):
-        raise SketchMLException("order='blocked' over a sparse DataSet is not built here: a data.DenseDataSet has it")
-    return "blocked_"
+    dense = getattr(dataSet, "dense", False)
+    if order == "blocked" and not dense:
+        raise SketchMLException("order='blocked' over a sparse DataSet is not built here: a data.DenseDataSet has it, "
+                                "a sparse DataSet has order='segmented'")
+    if order == "segmented" and dense:
+        raise SketchMLException("order='segmented' is the sparse DataSet's order: a data.DenseDataSet has order='blocked'")
+    return order + "_"
 
 
 def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, want_pre: bool = False,
@@ -60,7 +65,9 @@ def batch_gradient(weight: torch.Tensor, dataSet, row0: int, batch: int, loss, w
     grad (dim values, unscaled), coef (-1.0 * loss.grad per instance), loss (per instance), pre (when
     asked for), nnz (toAuto's count of |grad| > 1e-8) and objLoss.  order="blocked" (a DenseDataSet only) takes
     skml_glm_gradient_dense_*blocked_*: the same sums in a fixed blocked order, deterministic and at memory
-    speed, not the bits of the reference's sequential `+=`."""
+    speed, not the bits of the reference's sequential `+=`.  order="segmented" (a sparse DataSet only) takes
+    skml_glm_gradient_segmented_*: pre, coef, loss and objLoss keep the sequential bits; grad[k] keeps them for a feature
+    of few window entries and is a fixed lane-strided, sliced sum for a wider one."""
     infix = _order_infix(dataSet, order)
     dev = weight.device
     if dataSet.device != dev:

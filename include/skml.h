@@ -630,6 +630,49 @@ int skml_glm_gradient_dense_lowp_blocked_f32(skml_ctx* ctx, const skml_glm_dense
  * 2) per element: out = lanes per row L, waves per row S, rows in flight per wave, RB, NB, bytes of partial
  * sums (0 with NB = 1).  -1 for any other x_bytes, or batch or dim outside [1, 2^31 - 1]. */
 int skml_debug_glm_dense_blocked_plan(int x_bytes, int64_t batch, int64_t dim, int64_t out[6]);
+/* The dense gradient of `models` = K models (1 .. 16) in one pass over the window of x: one-vs-rest classes, a
+ * sweep of learning rates or regularisers, several settings side by side.  K calls of the blocked entries read
+ * the window K times; these read it twice whatever K is, on the fp64 matrix instruction (pre = X . W^T, 16 rows x
+ * 16 models per accumulator; grad = Coef^T . X, 16 models x 16 columns per accumulator).  Arguments, NULL rules,
+ * the single synchronisation, stream behaviour and timing ids are the blocked entries'; every array is
+ * model-major, so row m of each output is what the single-model entry hands to skml_glm_finish_*, the optimiser
+ * update and the codecs:
+ *   w_dev       K x dim doubles (_f64) or floats (_f32), contiguous: each model's weight is an ordinary vector
+ *   labels_dev  K x rows doubles, or NULL: every model uses data->label
+ *   pre_out, coef_out, loss_out   K x batch (pre_out, loss_out may be NULL; a context buffer stands in for a NULL
+ *               coef_out);  grad_out  K x dim;  nnz_out[K], obj_loss_out[K]
+ * One loss_kind for all models.  The summation contract is the blocked one restated: all arithmetic in double
+ * over the exactly widened x, every sum from +0.0, no floating-point atomic, the order of every sum a function of
+ * batch, dim, K, the storage type and compile-time constants only, so the same call gives the same bits on every
+ * run.  The order in which the instruction adds its own four products is the hardware's, fixed but not specified
+ * here: no bit parity with the blocked or the sequential order is claimed, only the error bound of any order
+ * (|pre - exact| <= gamma_dim sum|x w|, |grad - exact| <= gamma_batch sum|x coef|).  coef, loss, objLoss and
+ * toAuto's count are computed from this pre and this grad as the blocked entries do.  NaN and Inf take part as in
+ * any IEEE sum; lanes that stand for rows past batch, columns past dim (pad elements included) or models past K
+ * feed +0.0 and load nothing.  The partial sums live in the context's staging buffer (at most 1 / 8 of the
+ * window's bytes of x).  SKML_E_ARG, with nothing written: everything the blocked entries refuse, models outside
+ * [1, 16], K x dim, K x batch or K x rows doubles beyond an int64, grad_out overlapping an input or another output. */
+int skml_glm_gradient_dense_multi_f64(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                      int32_t loss_kind, int32_t models, const double* w_dev, const double* labels_dev,
+                                      double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
+                                      double* obj_loss_out);
+int skml_glm_gradient_dense_multi_f32(skml_ctx* ctx, const skml_glm_dense_data* data, int64_t row0, int64_t batch,
+                                      int32_t loss_kind, int32_t models, const float* w_dev, const double* labels_dev,
+                                      double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,
+                                      double* obj_loss_out);
+int skml_glm_gradient_dense_lowp_multi_f64(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                           int32_t loss_kind, int32_t models, const double* w_dev, const double* labels_dev,
+                                           double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                           int64_t* nnz_out, double* obj_loss_out);
+int skml_glm_gradient_dense_lowp_multi_f32(skml_ctx* ctx, const skml_glm_dense_lowp_data* data, int64_t row0, int64_t batch,
+                                           int32_t loss_kind, int32_t models, const float* w_dev, const double* labels_dev,
+                                           double* pre_out, double* coef_out, double* loss_out, double* grad_out,
+                                           int64_t* nnz_out, double* obj_loss_out);
+/* The plan of such a call (csrc/skml_glm_dense_multi.hpp; host arithmetic only): out = rows per tile of the row dot
+ * (16), tiles per wave R, waves per tile S, columns per lane step E, columns per wave of the column sum, RB, NB, bytes
+ * of partial sums (0 with NB = 1).  -1 for any other x_bytes, models outside [1, 16], or batch or dim outside
+ * [1, 2^31 - 1]. */
+int skml_debug_glm_dense_multi_plan(int x_bytes, int models, int64_t batch, int64_t dim, int64_t out[8]);
 /* skml_glm_gradient_* over the same skml_glm_data in the segmented summation order: opt-in twins for a caller
  * who needs a deterministic sparse gradient at memory speed, not the bits of the reference's sequential `+=`.
  * Arguments, outputs, NULL rules, refusals, the single synchronisation, stream behaviour and timing ids are the

@@ -145,6 +145,14 @@ def glm_dense_blocked_plan(x_bytes: int, batch: int, dim: int):
     return tuple(out) if lib.skml_debug_glm_dense_blocked_plan(int(x_bytes), int(batch), int(dim), out) == 0 else None
 
 
+def glm_dense_multi_plan(x_bytes: int, models: int, batch: int, dim: int):
+    """skml_debug_glm_dense_multi_plan: (rows per tile, tiles per wave R, waves per tile S, columns per lane step E,
+    columns per wave of the column sum, RB, NB, bytes of partial sums) of the K-model gradient over an x of x_bytes
+    per element; None for bad arguments."""
+    out = (C.c_int64 * 8)()
+    return tuple(out) if lib.skml_debug_glm_dense_multi_plan(int(x_bytes), int(models), int(batch), int(dim), out) == 0 else None
+
+
 class ValidResult(C.Structure):
     """skml_valid_result (include/skml.h): what one validation pass reads back."""
     _fields_ = [("loss", C.c_double), ("true_pos", C.c_int64), ("true_neg", C.c_int64), ("false_pos", C.c_int64),
@@ -255,6 +263,11 @@ _SIGS = {
     "skml_glm_gradient_dense_lowp_blocked_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_glm_gradient_dense_lowp_blocked_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_debug_glm_dense_blocked_plan": (C.c_int, [C.c_int, i64, i64, i64p]),
+    "skml_glm_gradient_dense_multi_f64": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_multi_f32": (C.c_int, [vp, C.POINTER(GlmDenseData), i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_lowp_multi_f64": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_glm_gradient_dense_lowp_multi_f32": (C.c_int, [vp, C.POINTER(GlmDenseLowpData), i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64p, dblp]),
+    "skml_debug_glm_dense_multi_plan": (C.c_int, [C.c_int, C.c_int, i64, i64, i64p]),
     "skml_glm_gradient_segmented_f64": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_glm_gradient_segmented_f32": (C.c_int, [vp, C.POINTER(GlmData), i64, i64, i32, vp, vp, vp, vp, vp, i64p, dblp]),
     "skml_debug_glm_segmented_constant": (C.c_int, [C.c_int]),

@@ -4,6 +4,7 @@
 // toAuto's count and objLoss.
 #include "skml_glm_dense.hpp"
 #include "skml_glm_dense_blocked.hpp"
+#include "skml_glm_dense_multi.hpp"
 #include "skml_glm_segmented.hpp"
 #include "skml_host.hpp"
 
@@ -221,6 +222,112 @@ int gradient_dense_lowp_blocked_x(skml_ctx* c, const skml_glm_dense_lowp_data* d
                                        loss_out, grad_out, nnz_out, obj_loss_out);
 }
 
+// The dense gradient of K <= 16 models in one pass over x (skml_glm_dense_multi.hip), once the struct is checked.
+// A sibling of gradient_dense_rest and gradient_run, which serve one model: the checks are theirs in their order
+// with K-fold ranges, the workspace holds K live counters and K objLoss (the same 256-byte head) ahead of the
+// K x batch stand-ins, and the one read-back brings 2 K scalars.  The partial sums live in the context's staging
+// buffer, reserved inside the column sum's step, after every check, as the blocked entries do.
+int gradient_dense_multi_rest(skml_ctx* c, const GlmBlockedX& bx, int x_bytes, size_t xb, int64_t row0, int64_t batch, int32_t loss_kind,
+                              int32_t models, const void* w, int wide, const double* labels, double* pre_out, double* coef_out,
+                              double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    const int64_t rows = bx.rows, dim = bx.dim;
+    if (row0 < 0 || row0 >= rows) return fail(SKML_E_ARG, "row0=%lld outside [0, %lld)", (long long)row0, (long long)rows);
+    if (batch < 1 || batch > rows)
+        return fail(SKML_E_ARG, "batch=%lld outside [1, %lld]: a window wraps at most once", (long long)batch, (long long)rows);
+    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
+        loss_kind != SKML_LOSS_L2_SQUARE)
+        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
+    if (models < 1 || models > kMulMaxModels) return fail(SKML_E_ARG, "models=%d outside [1, %d]", models, kMulMaxModels);
+    int64_t kb = 0, kd = 0, kr = 0;
+    if (!mul_bytes(models, batch, &kb) || !mul_bytes(models, dim, &kd) || !mul_bytes(models, rows, &kr))
+        return fail(SKML_E_ARG, "models=%d times batch, dim or rows doubles do not fit an int64", models);
+    const size_t bb = (size_t)kb, db = (size_t)kd;
+    const Range in[] = {{bx.x, xb, "x"}, {bx.label, (size_t)rows * 8, "label"}, {w, wide ? db : db / 2, "w"}, {labels, (size_t)kr, "labels"}};
+    const Range out[] = {{pre_out, bb, "pre_out"}, {coef_out, bb, "coef_out"}, {loss_out, bb, "loss_out"}};
+    const Range grad{grad_out, db, "grad_out"};
+    if (!bx.x || !bx.label || !w || !grad_out) return fail(SKML_E_ARG, "x, label, w or grad_out is NULL");
+    if (!nnz_out || !obj_loss_out) return fail(SKML_E_ARG, "nnz_out or obj_loss_out is NULL");
+    for (const Range& r : in)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    for (const Range& r : out)
+        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
+    if (!aligned8(grad_out)) return fail(SKML_E_ARG, "grad_out must be 8-byte aligned");
+    for (const Range& r : in)
+        if (overlap(grad, r)) return fail(SKML_E_ARG, "grad_out and %s overlap", r.name);
+    for (const Range& r : out) {
+        if (overlap(grad, r)) return fail(SKML_E_ARG, "grad_out and %s overlap", r.name);
+        for (const Range& q : in)
+            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
+    }
+    if (overlap(out[0], out[1]) || overlap(out[0], out[2]) || overlap(out[1], out[2]))
+        return fail(SKML_E_ARG, "pre_out, coef_out and loss_out overlap");
+    MulPlan plan;
+    if (!mul_plan(x_bytes, models, batch, dim, &plan)) return fail(SKML_E_ARG, "no plan for %d models, batch=%lld, dim=%lld", models, (long long)batch, (long long)dim);
+
+    HIP_TRY(hipSetDevice(c->device));
+    static_assert(kGlmHead >= 16 * kMulMaxModels, "K live counters and K objLoss ahead of the stand-in arrays");
+    const size_t need = kGlmHead + 2 * bb;
+    if (const int st = reserve(c, c->glm_ws, need, need + need / 4, "the mini-batch gradient's workspace")) return st;
+    char* base = static_cast<char*>(c->glm_ws.p);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(base);
+    double* obj = reinterpret_cast<double*>(base + 8 * kMulMaxModels);
+    double* coef = coef_out ? coef_out : reinterpret_cast<double*>(base + kGlmHead);
+    double* loss = loss_out ? loss_out : reinterpret_cast<double*>(base + kGlmHead + bb);
+    unsigned long long* pin = static_cast<unsigned long long*>(ctx_pinned(c, kGlmHead));
+    if (!pin) return fail(SKML_E_OOM, "pinned staging of the live counts and objLoss");
+
+    HIP_TRY(hipMemsetAsync(base, 0, kGlmHead, c->stream));
+    {
+        KernelTimer kt(c, SKML_K_GLM_PREDICT);
+        HIP_TRY(launch_glm_dense_multi_predict(c->stream, bx, row0, batch, loss_kind, w, wide, models, labels, pre_out, coef, loss));
+        HIP_TRY(launch_glm_dense_multi_loss_sum(c->stream, loss, batch, models, obj));
+    }
+    {
+        KernelTimer kt(c, SKML_K_GLM_PLUS_BY);
+        const size_t ws = (size_t)plan.ws_bytes;
+        if (ws)
+            if (const int st = reserve(c, c->stage, ws, ws + ws / 4, "the multi-model gradient's partial sums")) return st;
+        HIP_TRY(launch_glm_dense_multi_plus_by(c->stream, bx, row0, batch, coef, models, ws ? static_cast<double*>(c->stage.p) : nullptr,
+                                               grad_out, cnt));
+    }
+    HIP_TRY(hipMemcpyAsync(pin, base, kGlmHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int m = 0; m < models; m++) {
+        nnz_out[m] = (int64_t)pin[m];
+        __builtin_memcpy(&obj_loss_out[m], &pin[kMulMaxModels + m], 8);
+    }
+    return SKML_OK;
+}
+
+// gradient_dense_blocked_x for K models.
+int gradient_dense_multi_x(skml_ctx* c, const skml_glm_dense_data* d, int64_t row0, int64_t batch, int32_t loss_kind, int32_t models,
+                           const void* w, int wide, const double* labels, double* pre_out, double* coef_out, double* loss_out,
+                           double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
+        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
+    size_t xb = 0;
+    if (!dense_bytes(d->rows, d->dim, &xb))
+        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
+    const GlmBlockedX bx{d->rows, d->dim, d->dim, d->x, d->label, kBlkXF64};
+    return gradient_dense_multi_rest(c, bx, 8, xb, row0, batch, loss_kind, models, w, wide, labels, pre_out, coef_out, loss_out, grad_out,
+                                     nnz_out, obj_loss_out);
+}
+
+// gradient_dense_lowp_blocked_x for K models.
+int gradient_dense_lowp_multi_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int64_t row0, int64_t batch, int32_t loss_kind,
+                                int32_t models, const void* w, int wide, const double* labels, double* pre_out, double* coef_out,
+                                double* loss_out, double* grad_out, int64_t* nnz_out, double* obj_loss_out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    size_t xb = 0;
+    if (const int st = dense_lowp_check(d, &xb)) return st;
+    const GlmBlockedX bx{d->rows, d->dim, d->pitch, d->x, d->label, d->x_kind};
+    return gradient_dense_multi_rest(c, bx, 16 / lowp_elems_per_group(d->x_kind), xb, row0, batch, loss_kind, models, w, wide, labels, pre_out,
+                                     coef_out, loss_out, grad_out, nnz_out, obj_loss_out);
+}
+
 int finish_x(skml_ctx* c, const int32_t* keys, bool kv, double* vals, int64_t n, int64_t dim, double times, int32_t reg_kind,
              double reg_param, const void* w, int32_t w_fp32) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
@@ -323,6 +430,33 @@ int skml_debug_glm_dense_blocked_plan(int x_bytes, int64_t batch, int64_t dim, i
     out[3] = p.rb;
     out[4] = p.nb;
     out[5] = p.ws_bytes;
+    return 0;
+}
+
+#define SKML_MULTI_ENTRY(name, data_t, w_t, fn, wide)                                                                                \
+    int name(skml_ctx* c, const data_t* data, int64_t row0, int64_t batch, int32_t loss_kind, int32_t models, const w_t* w,          \
+             const double* labels, double* pre_out, double* coef_out, double* loss_out, double* grad_out, int64_t* nnz_out,          \
+             double* obj_loss_out) {                                                                                                 \
+        return fn(c, data, row0, batch, loss_kind, models, w, wide, labels, pre_out, coef_out, loss_out, grad_out, nnz_out,          \
+                  obj_loss_out);                                                                                                     \
+    }
+SKML_MULTI_ENTRY(skml_glm_gradient_dense_multi_f64, skml_glm_dense_data, double, gradient_dense_multi_x, 1)
+SKML_MULTI_ENTRY(skml_glm_gradient_dense_multi_f32, skml_glm_dense_data, float, gradient_dense_multi_x, 0)
+SKML_MULTI_ENTRY(skml_glm_gradient_dense_lowp_multi_f64, skml_glm_dense_lowp_data, double, gradient_dense_lowp_multi_x, 1)
+SKML_MULTI_ENTRY(skml_glm_gradient_dense_lowp_multi_f32, skml_glm_dense_lowp_data, float, gradient_dense_lowp_multi_x, 0)
+#undef SKML_MULTI_ENTRY
+
+int skml_debug_glm_dense_multi_plan(int x_bytes, int models, int64_t batch, int64_t dim, int64_t out[8]) {
+    MulPlan p;
+    if (!out || !mul_plan(x_bytes, models, batch, dim, &p)) return -1;
+    out[0] = kMulTileRows;
+    out[1] = p.tiles_per_wave;
+    out[2] = p.split;
+    out[3] = p.lane_cols;
+    out[4] = p.strip_cols;
+    out[5] = p.rb;
+    out[6] = p.nb;
+    out[7] = p.ws_bytes;
     return 0;
 }
 

@@ -315,6 +315,15 @@ hipError_t launch_glm_dense_blocked_predict(hipStream_t st, const GlmBlockedX& d
 // partial: blk_plan's ws_bytes (skml_glm_dense_blocked.hpp), may be null when that is 0
 hipError_t launch_glm_dense_blocked_plus_by(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, const double* coef,
                                             double* partial, double* g, unsigned long long* count);
+// ---- dense instances, K <= 16 models per pass on the fp64 matrix instruction (skml_glm_dense_multi.hip) ----
+// w: K x dim, labels: K x rows or null (d.label for every model), pre / coef / loss: K x batch, all model-major
+hipError_t launch_glm_dense_multi_predict(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, int loss_kind, const void* w,
+                                          int wide, int models, const double* labels, double* pre, double* coef, double* loss);
+// obj[m] = the sum of loss[m][0 .. batch) in launch_glm_loss_sum's shape, one workgroup per model
+hipError_t launch_glm_dense_multi_loss_sum(hipStream_t st, const double* loss, int64_t batch, int models, double* obj);
+// partial: mul_plan's ws_bytes (skml_glm_dense_multi.hpp), may be null when that is 0; g: K x dim; count[K], zeroed by the caller
+hipError_t launch_glm_dense_multi_plus_by(hipStream_t st, const GlmBlockedX& d, int64_t row0, int64_t batch, const double* coef, int models,
+                                          double* partial, double* g, unsigned long long* count);
 // ---- the sparse column sum in the segmented summation order (skml_glm_segmented.hip) ----
 // stage: seg_stage_bytes(d.dim, d.nnz) bytes (skml_glm_segmented.hpp) that no other work on st uses
 hipError_t launch_glm_segmented_plus_by(hipStream_t st, const skml_glm_data& d, int64_t row0, int64_t batch, const double* coef,

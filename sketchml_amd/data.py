@@ -71,6 +71,17 @@ def _device(device):
     return dev
 
 
+def one_vs_rest_labels(y, classes, device=None) -> torch.Tensor:
+    """The K x rows matrix of +-1.0 labels of K one-vs-rest models from a vector of class ids: row m is +1.0 where
+    y == classes[m] and -1.0 elsewhere (float64, contiguous, on the device), the `labels` of
+    optim.batch_gradient_multi.  classes: the K class ids, in the order of the models."""
+    y = torch.as_tensor(y).reshape(-1).to(_device(device))
+    ids = torch.as_tensor(classes).reshape(-1).to(device=y.device, dtype=y.dtype)
+    if ids.numel() < 1 or y.numel() < 1:
+        raise SketchMLException("one_vs_rest_labels needs at least one class and one instance")
+    return torch.where(y[None, :] == ids[:, None], 1.0, -1.0).to(torch.float64).contiguous()
+
+
 class DataSet:
     """ml/data/DataSet.scala over device tensors.
 

@@ -5,14 +5,11 @@
 
 #include <vector>
 
-#include "skml_glm_dense_lowp.hpp"
+#include "skml_glm_args.hpp"
 #include "skml_internal.h"
 #include "skml_sparse.h"
 
 namespace skml {
-
-// Sets the calling thread's skml_last_error message and returns `code` (skml_ctx.cpp).
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(expr)                                                                             \
     do {                                                                                          \
@@ -136,43 +133,20 @@ inline const skml_params* params_or_default(const skml_params* p, skml_params* d
     return def;
 }
 
-// What the argument checks of the entries share: a named byte range of a caller's array (a NULL or empty
-// range overlaps nothing), 8-byte alignment, and the largest length a Java int holds.
-struct Range {
-    const void* p;
+// Either dense data struct as the one view the blocked and the K-model kernels take, once its head is checked
+// (skml_glm_args.hpp): x_bytes is the storage width of an element, bytes the size of x.
+struct DenseView {
+    GlmBlockedX bx;
+    int x_bytes;
     size_t bytes;
-    const char* name;
 };
-inline bool overlap(const Range& a, const Range& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+inline int dense_view(const skml_glm_dense_data* d, DenseView* v) {
+    *v = {{d->rows, d->dim, d->dim, d->x, d->label, kBlkXF64}, 8, 0};
+    return dense_check(d, &v->bytes);
 }
-inline bool aligned8(const void* p) { return ((uintptr_t)p) % 8 == 0; }
-constexpr int64_t kJavaIntMax = 0x7FFFFFFFLL;
-// *bytes of the rows * dim doubles of a dense data set; false when rows * dim * 8 does not fit an int64
-inline bool dense_bytes(int64_t rows, int64_t dim, size_t* bytes) {
-    int64_t n;
-    if (__builtin_mul_overflow(rows, dim, &n) || n > INT64_MAX / 8) return false;
-    *bytes = (size_t)n * 8;
-    return true;
-}
-
-// What the entries over a skml_glm_dense_lowp_data check of the struct before anything else: rows and dim, the
-// kind, the pitch rule, and *bytes of the rows * pitch elements of x.
-inline int dense_lowp_check(const skml_glm_dense_lowp_data* d, size_t* bytes) {
-    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
-        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
-    const int64_t e = lowp_elems_per_group(d->x_kind);
-    if (!e) return fail(SKML_E_ARG, "unknown x_kind %d", d->x_kind);
-    if (d->pitch < d->dim || d->pitch % e)
-        return fail(SKML_E_ARG, "pitch=%lld is below dim=%lld or leaves a row off a 16-byte boundary (a multiple of %lld elements)",
-                    (long long)d->pitch, (long long)d->dim, (long long)e);
-    if (((uintptr_t)d->x) % 16) return fail(SKML_E_ARG, "x must be 16-byte aligned");
-    int64_t n;
-    if (__builtin_mul_overflow(d->rows, d->pitch, &n) || n > INT64_MAX / (16 / e))
-        return fail(SKML_E_ARG, "rows=%lld times pitch=%lld elements do not fit an int64", (long long)d->rows, (long long)d->pitch);
-    *bytes = (size_t)n * (size_t)(16 / e);
+inline int dense_view(const skml_glm_dense_lowp_data* d, DenseView* v) {
+    if (const int st = dense_lowp_check(d, &v->bytes)) return st;
+    *v = {{d->rows, d->dim, d->pitch, d->x, d->label, d->x_kind}, 16 / lowp_elems_per_group(d->x_kind), v->bytes};
     return SKML_OK;
 }
 

@@ -1,7 +1,8 @@
 // skml_valid_api.cpp -- host side of the validation pass of the C ABI (include/skml.h;
-// ml/util/ValidationUtil.scala:12-93): argument checks, the context buffer that holds the counters, the
-// stand-ins for the arrays the caller does not keep and the sort's scratch, the launches of
-// skml_glm.hip / skml_valid.hip and the one read-back through pinned staging.
+// ml/util/ValidationUtil.scala:12-93): each entry family is its argument checks (skml_glm_args.hpp), then
+// validate_run, which owns the context buffer that holds the counters, the stand-ins for the arrays the caller
+// does not keep and the sort's scratch, the launches of skml_glm.hip / skml_valid.hip and the one read-back
+// through pinned staging.
 #include "skml_host.hpp"
 
 using namespace skml;
@@ -107,124 +108,73 @@ int validate_run(skml_ctx* c, int64_t rows, const double* label, int32_t flags, 
     return SKML_OK;
 }
 
+// The loss, then the flag bits: what every validate entry checks after its data struct.
+int kind_check(int32_t loss_kind, int32_t flags) {
+    if (const int st = loss_check(loss_kind)) return st;
+    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    return SKML_OK;
+}
+
 int validate_x(skml_ctx* c, const skml_glm_data* d, int32_t loss_kind, const void* w, int wide, int32_t flags, double* pre_out,
                double* loss_out, skml_valid_result* out) {
     if (!c) return fail(SKML_E_ARG, "ctx is NULL");
     if (!d) return fail(SKML_E_ARG, "data is NULL");
     if (!out) return fail(SKML_E_ARG, "out is NULL");
-    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax || d->nnz < 0)
-        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1], or nnz=%lld < 0", (long long)d->rows,
-                    (long long)d->dim, (long long)d->nnz);
-    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
-        loss_kind != SKML_LOSS_L2_SQUARE)
-        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
-    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    if (const int st = sparse_check(d)) return st;
+    if (const int st = kind_check(loss_kind, flags)) return st;
     const size_t nz = (size_t)d->nnz, rb = (size_t)d->rows * 8;
     const Range in[] = {{d->row_ptr, ((size_t)d->rows + 1) * 8, "row_ptr"}, {d->col, nz * 4, "col"}, {d->val, nz * 8, "val"},
                         {d->label, rb, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
     const Range outs[] = {{pre_out, rb, "pre_out"}, {loss_out, rb, "loss_out"}};
     if (!d->row_ptr || !d->label || !w) return fail(SKML_E_ARG, "row_ptr, label or w is NULL");
     if (nz && (!d->col || !d->val)) return fail(SKML_E_ARG, "col or val is NULL");
-    for (const Range& r : in)
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-    for (const Range& r : outs) {
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-        for (const Range& q : in)
-            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
-    }
-    if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
+    if (const int st = ranges_check(in, 5, outs, 2, nullptr)) return st;
     return validate_run(c, d->rows, d->label, flags, pre_out, loss_out, out, [&](double* pre, double* loss, unsigned long long* head) {
         return launch_glm_valid(c->stream, *d, loss_kind, w, wide, glm_lanes_per_row(d->nnz, d->rows), pre, loss, head);
     });
 }
 
-// What the dense passes share once rows, dim and the xb bytes of x are checked: validate_x's other checks, then
-// the same validate_run.
-template <typename Launch>
-int validate_dense_rest(skml_ctx* c, int64_t rows, int64_t dim, const void* x, size_t xb, const double* label, int32_t loss_kind,
-                        const void* w, int wide, int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out,
-                        Launch launch) {
-    if (loss_kind != SKML_LOSS_L1_LOG && loss_kind != SKML_LOSS_L2_HINGE && loss_kind != SKML_LOSS_L2_LOG &&
-        loss_kind != SKML_LOSS_L2_SQUARE)
-        return fail(SKML_E_ARG, "unknown loss %d", loss_kind);
-    if (flags & ~(SKML_VALID_AUC | SKML_VALID_TREE_SUM)) return fail(SKML_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
-    const size_t rb = (size_t)rows * 8;
-    const Range in[] = {{x, xb, "x"}, {label, rb, "label"}, {w, (size_t)dim * (wide ? 8 : 4), "w"}};
+// The pass over either dense struct: LaunchValid is skml_glm_dense.hip's launcher or skml_glm_dense_lowp.hip's.
+template <typename Data, auto LaunchValid>
+int validate_dense_x(skml_ctx* c, const Data* d, int32_t loss_kind, const void* w, int wide, int32_t flags, double* pre_out,
+                     double* loss_out, skml_valid_result* out) {
+    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
+    if (!d) return fail(SKML_E_ARG, "data is NULL");
+    if (!out) return fail(SKML_E_ARG, "out is NULL");
+    DenseView v;
+    if (const int st = dense_view(d, &v)) return st;
+    if (const int st = kind_check(loss_kind, flags)) return st;
+    const size_t rb = (size_t)d->rows * 8;
+    const Range in[] = {{d->x, v.bytes, "x"}, {d->label, rb, "label"}, {w, (size_t)d->dim * (wide ? 8 : 4), "w"}};
     const Range outs[] = {{pre_out, rb, "pre_out"}, {loss_out, rb, "loss_out"}};
-    if (!x || !label || !w) return fail(SKML_E_ARG, "x, label or w is NULL");
-    for (const Range& r : in)
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-    for (const Range& r : outs) {
-        if (!aligned8(r.p)) return fail(SKML_E_ARG, "%s must be 8-byte aligned", r.name);
-        for (const Range& q : in)
-            if (overlap(r, q)) return fail(SKML_E_ARG, "%s and %s overlap", r.name, q.name);
-    }
-    if (overlap(outs[0], outs[1])) return fail(SKML_E_ARG, "pre_out and loss_out overlap");
-    return validate_run(c, rows, label, flags, pre_out, loss_out, out, launch);
-}
-
-int validate_dense_x(skml_ctx* c, const skml_glm_dense_data* d, int32_t loss_kind, const void* w, int wide, int32_t flags,
-                     double* pre_out, double* loss_out, skml_valid_result* out) {
-    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
-    if (!d) return fail(SKML_E_ARG, "data is NULL");
-    if (!out) return fail(SKML_E_ARG, "out is NULL");
-    if (d->rows < 1 || d->rows > kJavaIntMax || d->dim < 1 || d->dim > kJavaIntMax)
-        return fail(SKML_E_ARG, "rows=%lld or dim=%lld outside [1, 2^31 - 1]", (long long)d->rows, (long long)d->dim);
-    size_t xb = 0;
-    if (!dense_bytes(d->rows, d->dim, &xb))
-        return fail(SKML_E_ARG, "rows=%lld times dim=%lld doubles do not fit an int64", (long long)d->rows, (long long)d->dim);
-    return validate_dense_rest(c, d->rows, d->dim, d->x, xb, d->label, loss_kind, w, wide, flags, pre_out, loss_out, out,
-                               [&](double* pre, double* loss, unsigned long long* head) {
-                                   return launch_glm_dense_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
-                               });
-}
-
-int validate_dense_lowp_x(skml_ctx* c, const skml_glm_dense_lowp_data* d, int32_t loss_kind, const void* w, int wide,
-                          int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
-    if (!c) return fail(SKML_E_ARG, "ctx is NULL");
-    if (!d) return fail(SKML_E_ARG, "data is NULL");
-    if (!out) return fail(SKML_E_ARG, "out is NULL");
-    size_t xb = 0;
-    if (const int st = dense_lowp_check(d, &xb)) return st;
-    return validate_dense_rest(c, d->rows, d->dim, d->x, xb, d->label, loss_kind, w, wide, flags, pre_out, loss_out, out,
-                               [&](double* pre, double* loss, unsigned long long* head) {
-                                   return launch_glm_dense_lowp_valid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
-                               });
+    if (!d->x || !d->label || !w) return fail(SKML_E_ARG, "x, label or w is NULL");
+    if (const int st = ranges_check(in, 3, outs, 2, nullptr)) return st;
+    return validate_run(c, d->rows, d->label, flags, pre_out, loss_out, out, [&](double* pre, double* loss, unsigned long long* head) {
+        return LaunchValid(c->stream, *d, loss_kind, w, wide, pre, loss, head);
+    });
 }
 
 }  // namespace
 
 extern "C" {
 
-int skml_glm_validate_f64(skml_ctx* c, const skml_glm_data* data, int32_t loss_kind, const double* w, int32_t flags,
-                          double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_x(c, data, loss_kind, w, 1, flags, pre_out, loss_out, out);
-}
-
-int skml_glm_validate_f32(skml_ctx* c, const skml_glm_data* data, int32_t loss_kind, const float* w, int32_t flags,
-                          double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
-}
-
-int skml_glm_validate_dense_f64(skml_ctx* c, const skml_glm_dense_data* data, int32_t loss_kind, const double* w, int32_t flags,
-                                double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_dense_x(c, data, loss_kind, w, 1, flags, pre_out, loss_out, out);
-}
-
-int skml_glm_validate_dense_f32(skml_ctx* c, const skml_glm_dense_data* data, int32_t loss_kind, const float* w, int32_t flags,
-                                double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_dense_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
-}
-
-int skml_glm_validate_dense_lowp_f64(skml_ctx* c, const skml_glm_dense_lowp_data* data, int32_t loss_kind, const double* w,
-                                     int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_dense_lowp_x(c, data, loss_kind, w, 1, flags, pre_out, loss_out, out);
-}
-
-int skml_glm_validate_dense_lowp_f32(skml_ctx* c, const skml_glm_dense_lowp_data* data, int32_t loss_kind, const float* w,
-                                     int32_t flags, double* pre_out, double* loss_out, skml_valid_result* out) {
-    return validate_dense_lowp_x(c, data, loss_kind, w, 0, flags, pre_out, loss_out, out);
-}
+// The validate entries only forward: `...` is the family's function above, w_t the weight's type.
+#define SKML_VALIDATE_ENTRY(name, data_t, w_t, ...)                                                                          \
+    int name(skml_ctx* c, const data_t* data, int32_t loss_kind, const w_t* w, int32_t flags, double* pre_out, double* loss_out, \
+             skml_valid_result* out) {                                                                                       \
+        return __VA_ARGS__(c, data, loss_kind, w, sizeof(w_t) == 8, flags, pre_out, loss_out, out);                          \
+    }
+#define SKML_DENSE_VALID validate_dense_x<skml_glm_dense_data, launch_glm_dense_valid>
+#define SKML_LOWP_VALID validate_dense_x<skml_glm_dense_lowp_data, launch_glm_dense_lowp_valid>
+SKML_VALIDATE_ENTRY(skml_glm_validate_f64, skml_glm_data, double, validate_x)
+SKML_VALIDATE_ENTRY(skml_glm_validate_f32, skml_glm_data, float, validate_x)
+SKML_VALIDATE_ENTRY(skml_glm_validate_dense_f64, skml_glm_dense_data, double, SKML_DENSE_VALID)
+SKML_VALIDATE_ENTRY(skml_glm_validate_dense_f32, skml_glm_dense_data, float, SKML_DENSE_VALID)
+SKML_VALIDATE_ENTRY(skml_glm_validate_dense_lowp_f64, skml_glm_dense_lowp_data, double, SKML_LOWP_VALID)
+SKML_VALIDATE_ENTRY(skml_glm_validate_dense_lowp_f32, skml_glm_dense_lowp_data, float, SKML_LOWP_VALID)
+#undef SKML_VALIDATE_ENTRY
+#undef SKML_DENSE_VALID
+#undef SKML_LOWP_VALID
 
 int skml_auc_rank_sum(skml_ctx* c, const double* scores, const double* labels, int64_t n, int32_t* order_out, int64_t* pos,
                       int64_t* neg, uint64_t* rank_sum, int64_t* nan_scores) {

@@ -165,21 +165,13 @@ class GradientDescent:
         losses, which stay in self.lastLoss; with sequentialLoss it is their sum in batch order
         (skml_glm_seq_sum), the reference's `objLoss += ...` bit for bit given the losses.  order: batch_gradient's."""
         _order_infix(dataSet, order)  # refused before the data set's read index moves
-        batchSize = int(dataSet.size * self.batchSpRatio)
-        if batchSize == 0 or self.batchSpRatio > 1:
-            raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
-                                    f"{batchSize}: the reference divides by zero, or reads an instance twice")
+        batchSize = self._batch_size(dataSet)
         self._check_weight(weight)
         if dataSet.dim != self.dim:
             raise SketchMLException(f"the data set has {dataSet.dim} features, the optimiser {self.dim}")
         out = batch_gradient(weight, dataSet, dataSet.take(batchSize), batchSize, loss, order=order)
         self.lastLoss = out["loss"]
-        if auto_dense(out["nnz"], self.dim):
-            grad = DenseDoubleGradient(self.dim, out["grad"])
-        else:
-            keys, vals = to_sparse(out["grad"])  # toSparse of the unscaled values
-            grad = SparseDoubleGradient(self.dim, keys, vals)
-        finish_gradient(grad, 1.0 / batchSize, loss, weight)
+        grad = self._finished(out["grad"], out["nnz"], batchSize, loss, weight)
         regLoss = float(loss.getReg(weight))
         objLoss = out["objLoss"]
         if sequentialLoss:
@@ -196,10 +188,7 @@ class GradientDescent:
         self.lastLoss and the counters step once.  Each model's update is the caller's, with its own optimiser state."""
         if not getattr(dataSet, "dense", False):
             raise SketchMLException("miniBatchGradientDescentMulti over a sparse DataSet is not built here: a data.DenseDataSet has it")
-        batchSize = int(dataSet.size * self.batchSpRatio)
-        if batchSize == 0 or self.batchSpRatio > 1:
-            raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
-                                    f"{batchSize}: the reference divides by zero, or reads an instance twice")
+        batchSize = self._batch_size(dataSet)
         if weights.dim() != 2 or weights.shape[1] != self.dim or dataSet.dim != self.dim:
             raise SketchMLException(f"weights {tuple(weights.shape)}, the data set has {dataSet.dim} features, the optimiser {self.dim}")
         for m in range(weights.shape[0]):
@@ -210,15 +199,28 @@ class GradientDescent:
         self.lastLoss = out["loss"]
         result = []
         for m in range(weights.shape[0]):
-            if auto_dense(out["nnz"][m], self.dim):
-                grad = DenseDoubleGradient(self.dim, out["grad"][m])
-            else:
-                keys, vals = to_sparse(out["grad"][m])  # toSparse of the unscaled values
-                grad = SparseDoubleGradient(self.dim, keys, vals)
-            finish_gradient(grad, 1.0 / batchSize, loss, weights[m])
+            grad = self._finished(out["grad"][m], out["nnz"][m], batchSize, loss, weights[m])
             result.append((grad, batchSize, out["objLoss"][m], float(loss.getReg(weights[m]))))
         self.nextBatch()
         return result
+
+    def _batch_size(self, dataSet) -> int:
+        """(size * batchSpRatio).toInt, refused where the reference divides by zero or reads an instance twice."""
+        batchSize = int(dataSet.size * self.batchSpRatio)
+        if batchSize == 0 or self.batchSpRatio > 1:
+            raise SketchMLException(f"batchSpRatio={self.batchSpRatio} over {dataSet.size} instances gives a batch of "
+                                    f"{batchSize}: the reference divides by zero, or reads an instance twice")
+        return batchSize
+
+    def _finished(self, values: torch.Tensor, nnz: int, batchSize: int, loss, weight: torch.Tensor):
+        """One model's unscaled gradient as toAuto's choice, scaled by 1.0 / batchSize and regularised against weight."""
+        if auto_dense(nnz, self.dim):
+            grad = DenseDoubleGradient(self.dim, values)
+        else:
+            keys, vals = to_sparse(values)  # toSparse of the unscaled values
+            grad = SparseDoubleGradient(self.dim, keys, vals)
+        finish_gradient(grad, 1.0 / batchSize, loss, weight)
+        return grad
 
     def nextBatch(self) -> None:
         """The counters' step at the end of miniBatchGradientDescent (GradientDescent.scala:48-49)."""
